@@ -9,19 +9,23 @@ the 1000 G1 Lagrange combines of the first t = 334 VERIFIED shares of every ciph
 A step = one such epoch through the HIP path; inputs (compressed shares as on the wire, per-
 ciphertext H = hash_g1_g2(u, v) and w, the node index of every share) are already resident in
 HBM when the timed region starts; decode + subgroup checks are inside it.  ~1% of shares are
-corrupted (valid points, wrong share) and a few carry invalid encodings; decisions are checked
-against the construction after timing.
+corrupted (valid points, wrong share) and a few carry invalid encodings; with --full the decisions
+are checked against the construction after timing.
+
+A plain run sets up, warms up, times --steps epochs, writes the last timed epoch's outputs when
+--dump-outputs DIR is given (same arguments, same inputs, run after run) and prints the headline
+line.  --full adds everything else described below after the timed steps.
 
 Multi-GPU (strong scaling, the default for --gpus N > 1): one process per GPU
 (torch.distributed.run), the SAME C3 epoch split over the ranks by hbtc_shard_instances (whole
 ciphertexts, balanced by share count; hbbft_amd/shard.py): every rank verifies and combines its
 ciphertexts, then one RCCL all-gather over xGMI merges the verdicts and combined points into the
 whole epoch's arrays on every rank (the north star's only collective), ordered behind the
-library's streams with hbtc_stream_wait_ctx.  The merged epoch is checked against the
+library's streams with hbtc_stream_wait_ctx.  With --full the merged epoch is checked against the
 construction after timing.  --scaling weak runs an independent 1000-ciphertext epoch per rank
 instead (no collective).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with "roofline" (the longest
+Prints ONE JSON line on rank 0; with --full it also holds "roofline" (the longest
 critical-path kernel of the default RLC mode; Fqm counted by tools/fqm_count.cpp ->
 bench/roofline_constants.json; HBM traffic from the committed PMC passes), "cpu_baseline" (the
 oracle's threshold_crypto restatement timed on this host), and at N = 1 two more measured
@@ -322,7 +326,8 @@ class NodeEpoch:
         self.node.verify_dec_shares_dev(self.keyset, parts)
         self.node.combine_dec_verified_dev(parts, self.t)
 
-    def check(self, ctx, args):
+    def results(self):
+        """(status, g, cst) of the last step: the slots' slices of the epoch, in order."""
         self.node.sync()
         st, g, cst = [], [], []
         for c, ep in zip(self.ctxs, self.eps):
@@ -331,7 +336,10 @@ class NodeEpoch:
                 st.append(a)
                 g.append(b)
                 cst.append(x)
-        st, g, cst = np.concatenate(st), np.concatenate(g), np.concatenate(cst)
+        return np.concatenate(st), np.concatenate(g), np.concatenate(cst)
+
+    def check(self, ctx, args):
+        st, g, cst = self.results()
         expected = np.concatenate([ep.expected for ep in self.eps])
         want, _ = ctx.g1_mul(G1_GEN, scalars_bytes(_all_master_r(args, self.eps[0])))
         return (int((st != expected).sum()), bool((cst == 0).all() and bytes(g) == bytes(want)),
@@ -475,6 +483,33 @@ def timed(ctx, ep, steps, warmup, dist=None, gather=None, sync_all=None):
     return dt
 
 
+DUMP_MAX_SHARES = 4 << 20  # verdicts written in full up to here (16 MB), else a sample this long
+DUMP_MAX_CTS = 1 << 16     # combined points / combine statuses likewise (12.5 MB + 0.25 MB)
+
+
+def dump_outputs(dirname, st, g, cst):
+    """--dump-outputs: the arrays a caller of the timed path receives from one epoch, as float32
+    .npy files (every value is a small integer, exact in float32): status.npy (one verdict per
+    share), combined_g1.npy (ciphertexts x 48 bytes of the compressed combined points) and
+    combine_status.npy (one per ciphertext).  Past DUMP_MAX_SHARES verdicts / DUMP_MAX_CTS
+    ciphertexts a fixed seeded sample of the rows is written (the same rows in every run of the
+    same arguments): at most 16 + 12.5 + 0.25 MB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+
+    def rows(a, cap):
+        if len(a) <= cap:
+            return a
+        return a[np.sort(rng.choice(len(a), cap, replace=False))]
+
+    st = rows(np.asarray(st), DUMP_MAX_SHARES)
+    pick = rows(np.arange(len(cst)), DUMP_MAX_CTS)
+    g = np.asarray(g, np.uint8).reshape(-1, 48)[pick]
+    np.save(os.path.join(dirname, "status.npy"), st.astype(np.float32))
+    np.save(os.path.join(dirname, "combined_g1.npy"), g.astype(np.float32))
+    np.save(os.path.join(dirname, "combine_status.npy"), np.asarray(cst)[pick].astype(np.float32))
+
+
 def rlc_width_line(ctx, ep, args, bits):
     """The headline epoch with the other RLC scalar width (hbtc_set_rlc_bits): 64-bit scalars
     give <= 2^-64 per group check, 128-bit <= 2^-128 (DESIGN.md §4 "Soundness").  Same epoch,
@@ -548,8 +583,16 @@ def main():
                     help="ciphertexts per epoch (strong: of the whole job; weak: per GPU)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the adversarial / host-buffer lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the results against the construction and "
+                         "report the isolated epoch, the per-kernel spans and roofline, the other RLC "
+                         "width, the host-buffer and adversarial lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (statuses, combined points, combine "
+                         "statuses) as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the other RLC width and the adversarial / host-buffer lines")
     ap.add_argument("--mode", choices=["rlc", "per_share"], default="rlc",
                     help="rlc: batched random-linear-combination checks with exact fallback "
                          "(default); per_share: one pairing check per share")
@@ -618,6 +661,53 @@ def main():
     elapsed = timed(ctx, ep, args.steps, args.warmup, dist, gather,
                     torch.cuda.synchronize if torch else None)
     elapsed = max_over_ranks(elapsed, dist, dev if args.backend == "nccl" else None)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: under strong scaling the merged epoch
+        dump_outputs(args.dump_outputs, *(gather.merged() if strong and "gather" not in DIAG_SKIP
+                                          else ep.results(ctx)))
+    job_shares = args.n * args.cts * (1 if args.scaling == "strong" else world)
+    job_cts = args.cts * (1 if args.scaling == "strong" else world)
+    value = job_shares * args.steps / elapsed
+    combines = job_cts * args.steps / elapsed
+    if strong:
+        coll = ("RCCL (nccl backend) all-gather over xGMI" if args.backend == "nccl"
+                else "gloo all-gather of host copies (rehearsal, not the product merge)")
+        par = ("strong: one epoch sharded by whole ciphertexts over %d rank(s), one process per GPU "
+               "(hbtc_shard_instances), %s of statuses + combined points" % (world, coll))
+    elif world > 1:
+        par = "weak: an independent epoch per GPU (%d GPUs), no collective" % world
+    else:
+        par = "1 GPU"
+    out = {
+        "metric": "verified BLS12-381 shares/sec (whole node) at N=1000; combines/sec",
+        "value": round(value, 1),
+        "unit": "shares/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if args.scaling == "strong" else "weak",
+        "vs_baseline": None,
+        "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (seeded key set, shares generated on device; %s + 8 bad encodings)"
+                % ("%g%% wrong shares" % (100 * args.corrupt) if args.corrupt_mode == "uniform"
+                   else "f = %d Byzantine senders send wrong shares on every ciphertext" % ep.f),
+        "config": {"workload": "C3 HoneyBadger epoch: %d ciphertexts x %d DecryptionShares verified + %d G1 combines (t=%d)%s"
+                   % (job_cts, args.n, job_cts, ep.t, "" if args.scaling == "strong" else " per GPU"),
+                   "N": args.n, "f": ep.f, "t": ep.t, "ciphertexts": job_cts,
+                   "shares_per_step": job_shares, "parallelism": par},
+        "combines_per_s": round(combines, 1),
+        "mode": args.mode,
+        "rlc_bits": args.rlc_bits,
+    }
+    if not args.full:
+        # a plain run: the headline alone (--full adds the checks and every other measurement)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     breakdown = {f: ctx.timing_read(f) for f in FAMS}
     leaves = ctx.rlc_last_leaves() if args.mode == "rlc" else ep.total
     # the same epoch once more with nothing else in flight (after the timed region): the dominant
@@ -652,10 +742,6 @@ def main():
         raise SystemExit("rank %d: results differ from the construction (%d mismatches, combine %s)"
                          % (rank, mism, comb_ok))
 
-    job_shares = args.n * args.cts * (1 if args.scaling == "strong" else world)
-    job_cts = args.cts * (1 if args.scaling == "strong" else world)
-    value = job_shares * args.steps / elapsed
-    combines = job_cts * args.steps / elapsed
     consts = json.load(open(os.path.join(ROOT, "bench", "roofline_constants.json")))
     n_tiles = ep.m * ((ep.n + 63) // 64)
     sched = ctx.check_schedule_for(n_tiles)
@@ -712,38 +798,8 @@ def main():
             rocprof_ms = round(sum(a[0] for a in avgs), 3)
             rocprof_n = min(a[1] for a in avgs)
             rocprof_src = "; ".join("%s: %s" % (k, a[2]) for k, a in zip(parts, avgs))
-    if strong:
-        coll = ("RCCL (nccl backend) all-gather over xGMI" if args.backend == "nccl"
-                else "gloo all-gather of host copies (rehearsal, not the product merge)")
-        par = ("strong: one epoch sharded by whole ciphertexts over %d rank(s), one process per GPU "
-               "(hbtc_shard_instances), %s of statuses + combined points" % (world, coll))
-    elif world > 1:
-        par = "weak: an independent epoch per GPU (%d GPUs), no collective" % world
-    else:
-        par = "1 GPU"
-    out = {
-        "metric": "verified BLS12-381 shares/sec (whole node) at N=1000; combines/sec",
-        "value": round(value, 1),
-        "unit": "shares/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong" if args.scaling == "strong" else "weak",
-        "vs_baseline": None,
-        "dtype": "u32 (381-bit Montgomery limbs)",
-        "data": "synthetic (seeded key set, shares generated on device; %s + 8 bad encodings)"
-                % ("%g%% wrong shares" % (100 * args.corrupt) if args.corrupt_mode == "uniform"
-                   else "f = %d Byzantine senders send wrong shares on every ciphertext" % ep.f),
-        "config": {"workload": "C3 HoneyBadger epoch: %d ciphertexts x %d DecryptionShares verified + %d G1 combines (t=%d)%s"
-                   % (job_cts, args.n, job_cts, ep.t, "" if args.scaling == "strong" else " per GPU"),
-                   "N": args.n, "f": ep.f, "t": ep.t, "ciphertexts": job_cts,
-                   "shares_per_step": job_shares, "parallelism": par},
-        "combines_per_s": round(combines, 1),
+    out.update({
         "accepted_per_step": n_acc,
-        "mode": args.mode,
-        "rlc_bits": args.rlc_bits,
         "check_schedule": SCHED_NAME[sched],
         "exact_single_share_checks_per_step_rank0": leaves,
         "kernel_event_spans_ms_per_step_rank0": per_step,
@@ -792,7 +848,7 @@ def main():
                                                                 * consts["mad_u64_u32_per_fqm"] / 64), 3)
                                              if valu_insts else None),
         },
-    }
+    })
     if world == 1 and not args.no_extra:
         # the other RLC width on the same epoch (SURVEY.md §7 step 5 specifies 128-bit scalars;
         # the headline runs the library default)
@@ -826,13 +882,19 @@ def node_main(args):
     nep = NodeEpoch(node, args, slices)
     log("node: setup %.1fs (%d shares over %d slots)" % (time.time() - t0, nep.total, len(slots)))
     elapsed = timed_node(nep, args.steps, args.warmup)
-    mism, comb_ok, n_acc = nep.check(ctx, args)
-    per = {f: round(nep.ctxs[0].timing_read(f)[0] / args.steps, 3) for f in FAMS
-           if nep.ctxs[0].timing_read(f)[1]}
-    log("node: %.3fs for %d steps; slot-0 event spans ms/step %s; mismatches %d, combine ok %s"
-        % (elapsed, args.steps, per, mism, comb_ok))
-    if mism or not comb_ok:
-        raise SystemExit("node: results differ from the construction (%d mismatches, combine %s)" % (mism, comb_ok))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *nep.results())
+    extra = {}
+    if args.full:
+        mism, comb_ok, n_acc = nep.check(ctx, args)
+        per = {f: round(nep.ctxs[0].timing_read(f)[0] / args.steps, 3) for f in FAMS
+               if nep.ctxs[0].timing_read(f)[1]}
+        log("node: %.3fs for %d steps; slot-0 event spans ms/step %s; mismatches %d, combine ok %s"
+            % (elapsed, args.steps, per, mism, comb_ok))
+        if mism or not comb_ok:
+            raise SystemExit("node: results differ from the construction (%d mismatches, combine %s)"
+                             % (mism, comb_ok))
+        extra = {"accepted_per_step": n_acc, "kernel_event_spans_ms_per_step_slot0": per}
     n_gpus = len(set(slots))
     out = {
         "metric": "verified BLS12-381 shares/sec (whole node) at N=1000; combines/sec",
@@ -851,9 +913,9 @@ def node_main(args):
                                   "ciphertexts per slot (hbtc_shard_instances); no collective (disjoint "
                                   "outputs)" % (len(slots), n_gpus)},
         "combines_per_s": round(args.cts * args.steps / elapsed, 1),
-        "accepted_per_step": n_acc, "mode": args.mode,
-        "kernel_event_spans_ms_per_step_slot0": per,
+        "mode": args.mode,
     }
+    out.update(extra)
     print(json.dumps(out), flush=True)
     node.close()
     ctx.close()
