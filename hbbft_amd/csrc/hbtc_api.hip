@@ -914,9 +914,14 @@ int rlc_dec_pass(hbtc_ctx* c, Keyset* ks, uint32_t n_ct, const uint32_t* offsets
   HB_TRY(items_gate(c, n_tiles));
   G1J* t1s = nullptr;
   if (rlc_items_split()) HB_TRY(wst(c, "rlc.t1", n_items, &t1s));
+  // the call's sender table [r_id] pk_id (scalars keyed by the sender: hbtc_rlc.hip); the probe
+  // pass has its own key and, under its workspace suffix, its own table
+  G1J* rpk = nullptr;
+  if (!exact) HB_TRY(wst(c, "rlc.rpk", ks->n, &rpk));
   HB_TRY(timed(c, "rlc_items", [&] {
     return launch_rlc_items(c->stream, n_tiles, tiles, d_idx, d_share, ks->pk, ks->st, ks->tab,
-                            ks->n, key, sus, sums, dec, d_status, t1s, c->lanes[c->lane].dec_done);
+                            ks->n, key, sus, sums, dec, d_status, t1s, rpk,
+                            c->lanes[c->lane].dec_done);
   }));
   c->lanes[c->lane].dec_rec = rlc_items_split();
   HB_TRY(items_mark(c));

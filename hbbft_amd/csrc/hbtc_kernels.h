@@ -83,11 +83,13 @@ struct PtXY {
 hipError_t launch_pk_table(hipStream_t s, const G1A* pk, const int32_t* pk_status, uint32_t n,
                            PtXY* tab, Fq* ws);
 // split item pass (k_rlc_decode + k_rlc_items): t1s is n_items G1J of workspace ([|x|] d)
+// rpk: n_pk G1J of per-call workspace, the sender table R_id = [r_id] pk_id the launch fills
+// before the item pass reads it (the scalars are keyed by the sender; unused when sus.all)
 bool rlc_items_split();
 hipError_t launch_rlc_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
                             const uint8_t* shares, const G1A* pk, const int32_t* pk_status,
                             const PtXY* pk_tab, uint32_t n_pk, RlcKey key, Suspects sus,
-                            TileSums* sums, G1A* dec, int32_t* status, G1J* t1s,
+                            TileSums* sums, G1A* dec, int32_t* status, G1J* t1s, G1J* rpk,
                             hipEvent_t after_decode = nullptr);
 // Final decisions; with last_bad != null, counts every sender's REJECTs in `rejects` and stamps
 // last_bad[i] = now for the senders with >= thresh of them (clearing the counts).

@@ -11,6 +11,17 @@
 // share makes the equation fail except with probability <= 2^-k per check (every point is in the
 // prime-order subgroup: decode checks it, so E_i has order 1 or r).
 //
+// Scalars per sender.  r_i is a function of (call key, sender id) -- rlc_digits(key, idx[i]), not
+// of the item index: a check is over one tile of one ciphertext, and its bound needs only that
+// the scalars of the shares INSIDE that tile are independent, uniform, secret and drawn after the
+// shares are fixed; which scalars other tiles and other ciphertexts use does not enter it, and
+// the call's bound is the union bound over its checks as before.  So R_id = [r_id] pk_id is
+// computed once per call for the key set's n_pk senders (k_rlc_rpk) instead of once per share,
+// and a share loads its 144-byte point.  Two entries of ONE sender inside one tile would share
+// a scalar (valid + D and valid - D would cancel): the duplicate guard of k_rlc_items keeps the
+// first such entry in the sums and sends every later one to the exact leaf checks, the tracked
+// senders' path.  Copies in different tiles are in different checks and need nothing.
+//
 // Single-error location.  Next to the plain sum the item pass also forms the position-weighted
 // sum (weights p_i distinct in [0, |G|): p_i = bitrev_k(i) for share i of a group of 2^k, which
 // the reduction tree forms with one doubling per level, rlc_common.h), so each group yields
@@ -30,8 +41,8 @@
 //                   child derived), single wrong shares located at every level
 //     k_chk_leaves  the exact per-share check for eighths with >= 2 wrong shares
 // Work per share in the honest case: decode + r_i d_i (the x-adic joint double-and-add, curve.h
-// xadic_mul_uniform) + r_i pk_i (mixed additions from the key set's fixed-base table) + a share
-// of the wave's reduction tree; the pairing work is per group.
+// xadic_mul_uniform) + a load of r_i pk_i from the call's sender table + a share of the wave's
+// reduction tree; the pairing work is per group.
 #include "rlc_common.h"
 
 #ifndef HBTC_PART
@@ -44,10 +55,11 @@ namespace hbtc {
 #if HBTC_IN_PART(6)
 // ------------------------------------------------------------------------------ per item
 // One wave per tile: decode every share (the subgroup test yields [|x|] d on the way), draw the
-// x-adic scalar r_i = d0 + d1 x + d2 mu + d3 mu x (four ChaCha20 digits of key.bits / 4 bits,
-// mu = -x^2 the eigenvalue of phi: 2^key.bits distinct residues mod r, rlc_common.h), compute
-// r_i d_i by one joint double-and-add over the digits' bits (curve.h xadic_mul_uniform) and
-// r_i pk_i from the fixed-base table, then the plain and weighted group sums.  Items that cannot be checked (decode error, unknown sender) get their final status
+// sender's x-adic scalar r_i = d0 + d1 x + d2 mu + d3 mu x (four ChaCha20 digits of key.bits / 4
+// bits, mu = -x^2 the eigenvalue of phi: 2^key.bits distinct residues mod r, rlc_common.h),
+// compute r_i d_i by one joint double-and-add over the digits' bits (curve.h xadic_mul_uniform),
+// load r_i pk_i from the call's sender table, then the plain and weighted group sums.  Items
+// that cannot be checked (decode error, unknown sender) get their final status
 // here and contribute the identity; a ciphertext whose own H / w failed to decode is resolved
 // by k_rlc_finalize.  Needs nothing from the per-ciphertext preparation, so it runs
 // concurrently with k_g2_prepare on another stream.
@@ -120,12 +132,25 @@ __global__ void __launch_bounds__(64, HBTC_RLC_DEC_WAVES) k_rlc_decode(
 }
 #endif
 
+// The call's sender table R_id = [r_id] pk_id (rlc_common.h rlc_sender_point), 64 senders per
+// workgroup, on the call's stream ahead of the item pass.  A kernel of its own: as tail
+// workgroups of k_rlc_decode it cost that kernel 8 B/lane of scratch (192 -> 200).
+__global__ void __launch_bounds__(64) k_rlc_rpk(const G1A* __restrict__ pk,
+                                                const int32_t* __restrict__ pk_status,
+                                                const PtXY* __restrict__ pk_tab, uint32_t n_pk,
+                                                RlcKey key, G1J* __restrict__ rpk) {
+  const uint32_t id = blockIdx.x * 64u + threadIdx.x;
+  if (id >= n_pk) return;
+  G1J r;
+  rlc_sender_point(r, id, pk, pk_status, pk_tab, key);
+  rpk[id] = r;
+}
+
 __global__ void __launch_bounds__(64, HBTC_ITEMS_WAVES) k_rlc_items(
     const Tile* __restrict__ tiles, const uint32_t* __restrict__ idx,
-    const uint8_t* __restrict__ shares, const G1A* __restrict__ pk,
-    const int32_t* __restrict__ pk_status, const PtXY* __restrict__ pk_tab, uint32_t n_pk,
+    const uint8_t* __restrict__ shares, const int32_t* __restrict__ pk_status, uint32_t n_pk,
     RlcKey key, Suspects sus, TileSums* __restrict__ sums, G1A* __restrict__ dec,
-    int32_t* __restrict__ status, const G1J* __restrict__ t1s) {
+    int32_t* __restrict__ status, const G1J* __restrict__ t1s, const G1J* __restrict__ rpk) {
 #if HBTC_ITEMS_PRIO > 0
   __builtin_amdgcn_s_setprio(HBTC_ITEMS_PRIO);
 #endif
@@ -141,63 +166,82 @@ __global__ void __launch_bounds__(64, HBTC_ITEMS_WAVES) k_rlc_items(
   G1J S, P;
   jac_set_inf(S);
   jac_set_inf(P);
-  bool leaf = false;
+  int32_t st = HBTC_RLC_PENDING;
+  uint32_t id = 0;
+  bool sum = false;  // this share enters the group sums
+#if !HBTC_RLC_SPLIT
+  G1A d;
+  G1J t1;
+#endif
   if (lane < tile.count) {
-    int32_t st = HBTC_RLC_PENDING;
-    const uint32_t id = idx[item];
+    id = idx[item];
     if (id >= n_pk) {
       st = HBTC_UNKNOWN_SENDER;
     } else if (pk_status[id] != HBTC_ACCEPT) {
       st = HBTC_DECODE_ERR;
     } else {
-      G1A d;
-      G1J t1;  // [|x|] d from the subgroup test: [x] d = -t1, the x-adic table's second entry
 #if HBTC_RLC_SPLIT
       const bool dec_ok = status[item] != HBTC_DECODE_ERR;  // k_rlc_decode ran first
-      if (dec_ok) {
-        d = dec[item];
-        t1 = t1s[item];
-      }
 #else
       uint32_t w[12];
       rlc_load_words(w, shares, item, 12);
       const bool dec_ok = g1_decompress_t1(d, t1, w);
+      if (dec_ok) dec[item] = d;  // for the exact leaf checks and the combine (no second decode)
 #endif
       if (!dec_ok) {
         st = HBTC_DECODE_ERR;
+      } else if (is_suspect(sus, id)) {
+        st = HBTC_RLC_LEAF;  // straight to an exact check, outside the group sums
       } else {
-#if !HBTC_RLC_SPLIT
-        dec[item] = d;  // for the exact leaf checks and the combine (no second decode)
-#endif
-        if (is_suspect(sus, id)) {
-          st = HBTC_RLC_LEAF;  // straight to an exact check, outside the group sums
-        } else {
-          const XDigits xd = rlc_digits(key, item);
-          if (!d.inf) {
-            jac_neg(t1, t1);
-            Fq beta;
-            fq_set(beta, G1_BETA);
-#if HBTC_XADIC8
-#if HBTC_ITEMS_WAVES >= 2 && HBTC_SAC8_LDS
-            xadic_mul_sac8<Fq, true>(S, d, t1, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits,
-                                     reinterpret_cast<uint32_t*>(red), lane);
-#else
-            xadic_mul_sac8(S, d, t1, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits);
-#endif
-#else
-            G1A xp, pxp;
-            xadic_table(xp, pxp, d, t1);
-            xadic_mul_uniform(S, d, xp, pxp, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits);
-#endif
-          }
-          if (!pk[id].inf) rlc_pk_mul_x(P, pk_tab + (size_t)id * PK_TAB_WIN * 256, xd);
-        }
+        sum = true;
       }
     }
-    status[item] = st;
-    leaf = st == HBTC_RLC_LEAF;
   }
-  rlc_list_leaf(sus, leaf, (uint32_t)item, tile.inst, lane);
+  // Duplicate guard.  The scalar is keyed by the sender, so two entries of one sender in this
+  // tile would share it and a pair valid + D, valid - D would cancel in the sums: every later
+  // copy among the entries that enter the sums takes the tracked senders' path (the identity
+  // here, an exact check in k_chk_leaves); the first stays.  Wave-uniform: all 64 lanes shuffle.
+  {
+    const uint32_t mine = sum ? id : 0xffffffffu;
+    bool dup = false;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 63; ++j) {
+      const uint32_t other = (uint32_t)__shfl((int)mine, (int)j);
+      dup |= j < lane && other == mine;
+    }
+    if (sum && dup) {
+      sum = false;
+      st = HBTC_RLC_LEAF;
+    }
+  }
+  // statuses and the leaf list first: nothing of them stays live across the multiplication
+  if (lane < tile.count) status[item] = st;
+  rlc_list_leaf(sus, st == HBTC_RLC_LEAF, (uint32_t)item, tile.inst, lane);
+  if (sum) {
+#if HBTC_RLC_SPLIT
+    const G1A d = dec[item];
+    G1J t1 = t1s[item];  // [|x|] d from the subgroup test: [x] d = -t1, the x-adic table's second entry
+#endif
+    if (!d.inf) {
+      const XDigits xd = rlc_digits(key, id);
+      jac_neg(t1, t1);
+      Fq beta;
+      fq_set(beta, G1_BETA);
+#if HBTC_XADIC8
+#if HBTC_ITEMS_WAVES >= 2 && HBTC_SAC8_LDS
+      xadic_mul_sac8<Fq, true>(S, d, t1, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits,
+                               reinterpret_cast<uint32_t*>(red), lane);
+#else
+      xadic_mul_sac8(S, d, t1, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits);
+#endif
+#else
+      G1A xp, pxp;
+      xadic_table(xp, pxp, d, t1);
+      xadic_mul_uniform(S, d, xp, pxp, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits);
+#endif
+    }
+    P = rpk[id];  // [r_id] pk_id, the identity for a key at infinity
+  }
   TileSums* ts = sums + blockIdx.x;
   rlc_reduce_sp(redA, redB, S, P, lane, ts->S, ts->SW, ts->P, ts->PW, ts->SH, ts->SHW, ts->PH,
                 ts->PHW, ts->SQ, ts->SQW, ts->PQ, ts->PQW);
@@ -261,18 +305,24 @@ bool rlc_items_split() { return HBTC_RLC_SPLIT != 0; }
 hipError_t launch_rlc_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
                             const uint8_t* shares, const G1A* pk, const int32_t* pk_status,
                             const PtXY* pk_tab, uint32_t n_pk, RlcKey key, Suspects sus,
-                            TileSums* sums, G1A* dec, int32_t* status, G1J* t1s,
+                            TileSums* sums, G1A* dec, int32_t* status, G1J* t1s, G1J* rpk,
                             hipEvent_t after_decode) {
   if (n_tiles == 0) return hipSuccess;
+  hipError_t e;
+  // the sender table: not in the exact mode, where no share enters the sums
+  if (!sus.all && n_pk) {
+    hipLaunchKernelGGL(k_rlc_rpk, dim3(rlc_blocks(n_pk, 64)), dim3(64), 0, s, pk, pk_status, pk_tab,
+                       n_pk, key, rpk);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
 #if HBTC_RLC_SPLIT
   hipLaunchKernelGGL(k_rlc_decode, dim3(n_tiles), dim3(64), 0, s, tiles, idx, shares, pk_status, n_pk,
                      dec, t1s, status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess) return e;
   if (after_decode && (e = hipEventRecord(after_decode, s)) != hipSuccess) return e;
 #endif
-  hipLaunchKernelGGL(k_rlc_items, dim3(n_tiles), dim3(64), 0, s, tiles, idx, shares, pk, pk_status,
-                     pk_tab, n_pk, key, sus, sums, dec, status, t1s);
+  hipLaunchKernelGGL(k_rlc_items, dim3(n_tiles), dim3(64), 0, s, tiles, idx, shares, pk_status, n_pk,
+                     key, sus, sums, dec, status, t1s, rpk);
   return hipGetLastError();
 }
 hipError_t launch_rlc_finalize(hipStream_t s, uint32_t n_tiles, const Tile* tiles,

@@ -1,6 +1,8 @@
 // Device helpers shared by the RLC item passes of DecryptionShares (hbtc_rlc.hip) and
 // SignatureShares (hbtc_sig.hip): the per-call ChaCha20 scalars, the wave tree sums of a tile,
-// the fixed-base multiplication by a key-set share.  See hbtc_rlc.hip for the method.
+// the fixed-base multiplication by a key-set share.  See hbtc_rlc.hip for the method.  The
+// scalars are indexed by a 64-bit counter: the item index in the SignatureShare and pair-batch
+// passes, the sender id in the DecryptionShare pass (one scalar per sender and call).
 #pragma once
 #include "hbtc_kernels.h"
 
@@ -18,7 +20,7 @@ __device__ __forceinline__ void rlc_load_words(uint32_t* w, const uint8_t* base,
   }
 }
 
-// The scalar r_i = a + b mu of item i from a ChaCha20 block (RFC 8439 layout: constants, 8 key
+// The scalar r_i = a + b mu of counter value i (item or sender, above) from a ChaCha20 block (RFC 8439 layout: constants, 8 key
 // words, counter, 3 nonce words).  64-bit mode (key.bits = 64): a and b are the 32-bit words
 // [2j, 2j+1] of block i / 8 (j = i mod 8); 128-bit mode: a and b are the 64-bit pairs of words
 // [4j, 4j+1], [4j+2, 4j+3] of block i / 4 (j = i mod 4), under a different nonce word.
@@ -351,6 +353,18 @@ static __device__ void rlc_pk_mul_x(G1J& r, const PtXY* __restrict__ tab, const 
       jac_add_aff(r, r, q);
     }
   }
+}
+
+// Entry `id` of a DecryptionShare call's sender table: R_id = [r_id] pk_id for the scalar keyed
+// by the SENDER (rlc_digits(key, id)), once per call instead of once per share; the identity for
+// a key that failed to load (its fixed-base table entries are uninitialised and are not read) or
+// is the point at infinity.
+static __device__ void rlc_sender_point(G1J& r, uint32_t id, const G1A* __restrict__ pk,
+                                        const int32_t* __restrict__ pk_status,
+                                        const PtXY* __restrict__ pk_tab, const RlcKey& key) {
+  jac_set_inf(r);
+  if (pk_status[id] != HBTC_ACCEPT || pk[id].inf) return;
+  rlc_pk_mul_x(r, pk_tab + (size_t)id * PK_TAB_WIN * 256, rlc_digits(key, id));
 }
 
 // [a] pk + [b] phi(pk) from the key set's fixed-base table (2 nwin mixed additions, no

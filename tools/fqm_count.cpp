@@ -116,9 +116,10 @@ int main() {
   // RLC item (k_rlc_items): decode (the subgroup test yields [|x|] d), r*d by xadic_mul_sac8
   // (the sign-aligned 8-entry common-Z table, one mixed addition per digit bit, plus the even-d0
   // correction, computed by every lane) over nbits = 16 (64-bit RLC)
-  // or 32 (128-bit) digit bits, r*pk from the fixed-base table (4 nbits / 8 mixed additions, half
-  // of them with phi), and the item's share of the plain + position-weighted reduction tree of
-  // its tile: per side 3 * 63 Jacobian additions and 57 doublings, two sides, over 64 items
+  // or 32 (128-bit) digit bits, and the item's share of the plain + position-weighted reduction
+  // tree of its tile: per side 3 * 63 Jacobian additions and 57 doublings, two sides, over 64
+  // items.  r*pk costs the item nothing: the scalar is keyed by the sender and [r_id] pk_id comes
+  // from the call's sender table (n_pk fixed-base multiplications per call, not counted here)
   const uint32_t dg[4] = {0xa5a55a5au, 0x5a5aa5a5u, 0x3c3cc3c3u, 0xc3c33c3cu};
   G1J rd;  // a generic accumulator, for the tree costs below
   unsigned long long rlc_item = 0, rlc_item_128 = 0, jadd = 0, jdbl = 0;
@@ -152,14 +153,7 @@ int main() {
     xadic_table(xp, pxp, d2, t1);
     xadic_mul_uniform(rd, d2, xp, pxp, beta, dg[0] & m, dg[1] & m, dg[2] & m, dg[3] & m, nb);
 #endif
-    G1J rp;
-    jac_set_inf(rp);
-    jac_add_aff(rp, rp, gen1);
-    for (int a = 1; a < nb / 2; ++a) {  // 4 nb / 8 table additions, half with phi
-      G1A q = gen1;
-      if (a & 1) g1_phi(q, gen1);
-      jac_add_aff(rp, rp, q);
-    }
+    // r*pk is a load from the call's sender table (once per sender and call, not per item)
     (nb == 16 ? rlc_item : rlc_item_128) = hbtc_fqm_count + tree1;
   }
   // SignatureShare RLC item (k_sig_items): G2 decode + subgroup test, r*sigma by the
