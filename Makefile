@@ -3,6 +3,7 @@
 # so the groups build in parallel (`make -j8 lib`); hbtc_rlc.hip (parts 6-7) and hbtc_msm.hip
 # (parts 8-9) likewise.
 #   hosttest : the kernel arithmetic headers compiled for the HOST (tests/native, test-only)
+#   devtest  : the same headers behind a test-only device harness, once per Fq-product variant
 #   oracle   : the C restatement of threshold_crypto (oracle/c, test + CPU-baseline only)
 HIPCC ?= /opt/rocm/bin/hipcc
 CLANGXX ?= /opt/rocm/lib/llvm/bin/clang++
@@ -22,8 +23,8 @@ KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_P
          $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o
 LIB := hbbft_amd/libhbtc.so
 
-.PHONY: all lib hosttest oracle clean resources roofline-constants
-all: lib hosttest oracle
+.PHONY: all lib hosttest devtest oracle clean resources roofline-constants
+all: lib hosttest devtest oracle
 
 lib: $(LIB)
 
@@ -127,6 +128,20 @@ resources:
 hosttest: tests/native/libhbtc_hosttest.so
 tests/native/libhbtc_hosttest.so: tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -pthread -I$(CSRC) tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp -o $@
+
+# test-only device harness (tests/test_gpu_devarith.py): one object per variant of the Fq product,
+# each with the flags of the product objects that use that variant; the kernels and entry points
+# carry the variant's suffix, so the three link into one library
+DEVTEST_OBJS := $(BUILD)/hbtc_devtest.sr.o $(BUILD)/hbtc_devtest.inl.o $(BUILD)/hbtc_devtest.call.o
+$(BUILD)/hbtc_devtest.sr.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -DHBTC_GT_INLINE -c $< -o $@
+$(BUILD)/hbtc_devtest.inl.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
+$(BUILD)/hbtc_devtest.call.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+devtest: tests/native/libhbtc_devtest.so
+tests/native/libhbtc_devtest.so: $(DEVTEST_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 
 oracle: oracle/c/libtcoracle.so
 oracle/c/libtcoracle.so: oracle/c/tc_oracle.c

@@ -315,7 +315,7 @@ HD void fq_mul_ol(Fq& r, const Fq& a, const Fq& b) {
 // A sum of products of reduced operands (< 2p each) kept unreduced in 25 words and reduced ONCE:
 // fq_acc_mac is the product half of a Montgomery multiplication (144 v_mad_u64_u32), fq_acc_redc
 // the reduction half plus conditional subtractions of 4p and 2p (result < 2p).  At most 12
-// products per accumulator (< 48 p^2, so the Montgomery quotient is < 5.6p).  Device
+// products per accumulator (< 48 p^2, so the Montgomery quotient is < 5.876p < 6p).  Device
 // builds with the shared-subroutine product run both as subroutines on fixed registers (the
 // accumulator pinned to v60..v84 across calls: tools/gen_fips_asm.py); elsewhere plain C++ with
 // the same arithmetic (same Montgomery quotient, same subtractions: the same representative).
@@ -379,7 +379,7 @@ HD void fq_acc_redc(Fq& r, const FqAcc& acc) {
     for (int j = i + 12; j < 26; ++j) t[j] = addc32(t[j], 0, c, &c);
   }
   uint32_t x[12];
-  for (int i = 0; i < 12; ++i) x[i] = t[12 + i];  // < 5.6p: words 24, 25 are 0
+  for (int i = 0; i < 12; ++i) x[i] = t[12 + i];  // < 6p: words 24, 25 are 0
   for (int sh = 2; sh >= 1; --sh) {  // subtract 4p, then 2p, where they fit
     uint32_t m[12], d[12], b = 0;
     for (int i = 0; i < 12; ++i) m[i] = (FQ_P[i] << sh) | (i > 0 ? FQ_P[i - 1] >> (32 - sh) : 0u);
@@ -630,6 +630,16 @@ HD void fq_inv_binary(Fq& r, const Fq& a_mont) {
     uint32_t k = ctz31(d);
     shr_k(d, k);
     half_k(xd, k);
+    // ctz31 strips at most 31 bits: a difference with 32 or more trailing zeros (2^-32 per step
+    // for random operands; p - 1 and (p - 1) / 2 get there) is still even here, and left even it
+    // would make every later difference odd, the loop crawl and the bound above run out.  Finish
+    // the strip; the branch is wave-uniform and almost never taken.
+#pragma unroll 1
+    while (fq_wave_any(!done && (d.v[0] & 1u) == 0)) {
+      const uint32_t k2 = (done || (d.v[0] & 1u) != 0) ? 0u : ctz31(d);
+      shr_k(d, k2);
+      half_k(xd, k2);
+    }
     if (!done) {
       fq_sel(u, ge, d, u);
       fq_sel(x1, ge, xd, x1);

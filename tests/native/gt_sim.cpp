@@ -386,4 +386,38 @@ int ht_serial_check(const uint8_t* p1, const uint8_t* q1, const uint8_t* p2, con
   return fq12_is_one(e) ? 1 : 0;
 }
 
+// ht_gt_op / ht_gt_op_rep on RAW Montgomery limbs (no conversion: lazy representatives allowed):
+// a, b, out hold n items of six Fq2 coefficients f_0..f_5 in the flat basis, 24 little-endian
+// words each.  Returns 0, or 1 if the sub-lanes of a coefficient disagree (rep = 3).
+int ht_gt_op_raw(uint32_t n, uint32_t rep, const uint32_t* ops, const uint32_t* a, const uint32_t* b,
+                 uint32_t* out) {
+  int bad = 0;
+  for (uint32_t it = 0; it < n; ++it) {
+    const int op = (int)ops[it];
+    std::vector<Fq2> res(6 * rep);
+    run_lanes(6 * rep, [&](uint32_t l) {
+      const gt::Pos ps = gt::pos(rep);
+      Fq2 x, y, r;
+      memcpy(&x, a + 24 * (6 * it + ps.k), 96);
+      memcpy(&y, b + 24 * (6 * it + ps.k), 96);
+      switch (op) {
+        case 0: gt::mul(r, x, y, ps); break;
+        case 1: gt::sqr(r, x, ps); break;
+        case 2: r = x; gt::cyc_sqr(r, ps); break;
+        case 3: case 4: case 5: r = x; gt::frob(r, op - 2, ps); break;
+        case 6: r = x; gt::conj(r, ps); break;
+        case 7: gt::final_exp(r, x, ps); break;
+        case 8: gt::easy_part(r, x, ps); break;
+        default: gt::exp_by_x(r, x, ps); break;
+      }
+      res[l] = r;  // distinct slots per lane
+    });
+    for (uint32_t k = 0; k < 6; ++k) {
+      memcpy(out + 24 * (6 * it + k), &res[rep * k], 96);
+      for (uint32_t j = 1; j < rep; ++j) bad |= !fq2_eq(res[rep * k], res[rep * k + j]);
+    }
+  }
+  return bad;
+}
+
 }  // extern "C"

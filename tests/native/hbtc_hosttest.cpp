@@ -4,7 +4,7 @@
 // the product library.
 #include <cstring>
 
-#include "pairing.h"
+#include "pair.h"
 
 using namespace hbtc;
 
@@ -448,6 +448,116 @@ void ht_fr_div(const uint8_t* a32, const uint8_t* b32, uint8_t* out32) {
   fr_mul(r, am, bi);
   fr_from_mont(rc, r);
   store_words(out32, rc.v, 8);
+}
+
+// ---- raw-limb entries for tests/devarith_cases.py: operands and results are the Montgomery
+// limbs themselves (little-endian 32-bit words, 12 per Fq), no conversion, so the tests can feed
+// lazy representatives in [p, 2p).  The calling shapes are those of the device harness
+// (tests/native/hbtc_devtest.hip); here the C++ fallback paths run.
+int ht_fq_op(uint32_t n, const uint32_t* ops, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+             const uint32_t* d, uint32_t* out, uint32_t* flag) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fq A, Bv, C, D, r;
+    memcpy(A.v, a + 12 * i, 48);
+    memcpy(Bv.v, b + 12 * i, 48);
+    memcpy(C.v, c + 12 * i, 48);
+    memcpy(D.v, d + 12 * i, 48);
+    fq_zero(r);
+    uint32_t f = 0;
+    switch (ops[i]) {
+      case 0: fq_mul(r, A, Bv); break;
+      case 1: fq_sqr(r, A); break;
+      case 2: fq_mul_ol(r, A, Bv); break;
+      case 3: fq_add(r, A, Bv); break;
+      case 4: fq_sub(r, A, Bv); break;
+      case 5: fq_dbl(r, A); break;
+      case 6: fq_neg(r, A); break;
+      case 7: fq_canon(r, A); break;
+      case 8: f = fq_is_zero(A); break;
+      case 9: f = fq_eq(A, Bv); break;
+      case 10: fq_from_mont(r, A); break;
+      case 11: f = fq_is_lex_largest(A); break;
+      case 12: fq_inv_binary(r, A); break;
+      case 13: f = fq_sqrt(r, A); break;
+      case 14: fq_mul2(r, A, Bv, C, D); break;
+      default: return -1;
+    }
+    memcpy(out + 12 * i, r.v, 48);
+    flag[i] = f;
+  }
+  return 0;
+}
+
+// Lazy accumulators, 12 operand slots per item.  mode 0: nt x fq_acc_mac -> fq_acc_redc (out0);
+// 1: nt x fq_acc_mac2 -> fq_acc_redc2 (out1); 2: x = 0, y = 24 p^2, nt x fq_acc_macsub;
+// 3: x = y = 24 p^2, nt x fq_acc_subsub (2, 3: out0 = redc(x), out1 = redc2(y)).
+int ht_acc_op(uint32_t n, const uint32_t* mode, const uint32_t* nt, const uint32_t* a,
+              const uint32_t* b, uint32_t* out0, uint32_t* out1) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (mode[i] > 3 || nt[i] > 12) return -1;
+    FqAcc x, y;
+    fq_acc_zero(x);
+    fq_acc_zero(y);
+    if (mode[i] == 3) fq_acc_k24(x);
+    if (mode[i] >= 2) fq_acc_k24(y);
+    for (uint32_t t = 0; t < nt[i]; ++t) {
+      Fq A, Bv;
+      memcpy(A.v, a + 12 * (12 * i + t), 48);
+      memcpy(Bv.v, b + 12 * (12 * i + t), 48);
+      switch (mode[i]) {
+        case 0: fq_acc_mac(x, A, Bv); break;
+        case 1: fq_acc_mac2(y, A, Bv); break;
+        case 2: fq_acc_macsub(x, y, A, Bv); break;
+        default: fq_acc_subsub(x, y, A, Bv); break;
+      }
+    }
+    Fq r0, r1;
+    fq_acc_redc(r0, x);
+    fq_acc_redc2(r1, y);
+    memcpy(out0 + 12 * i, r0.v, 48);
+    memcpy(out1 + 12 * i, r1.v, 48);
+  }
+  return 0;
+}
+
+// The Karatsuba form of the GT code: fq_acc_k24(x), y = 0, nt x fq_acc_kara (term t: slots 2t,
+// 2t + 1 of a = a0, a1 and of b = b0, b1), then both reductions.  mode[i] must be 4.
+int ht_acc_kara(uint32_t n, const uint32_t* mode, const uint32_t* nt, const uint32_t* a,
+                const uint32_t* b, uint32_t* out0, uint32_t* out1) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (mode[i] != 4 || nt[i] > 6) return -1;
+    FqAcc x, y;
+    fq_acc_k24(x);
+    fq_acc_zero(y);
+    for (uint32_t t = 0; t < nt[i]; ++t) {
+      Fq a0, a1, b0, b1;
+      memcpy(a0.v, a + 12 * (12 * i + 2 * t), 48);
+      memcpy(a1.v, a + 12 * (12 * i + 2 * t + 1), 48);
+      memcpy(b0.v, b + 12 * (12 * i + 2 * t), 48);
+      memcpy(b1.v, b + 12 * (12 * i + 2 * t + 1), 48);
+      fq_acc_kara(x, y, a0, a1, b0, b1);
+    }
+    Fq r0, r1;
+    fq_acc_redc(r0, x);
+    fq_acc_redc2(r1, y);
+    memcpy(out0 + 12 * i, r0.v, 48);
+    memcpy(out1 + 12 * i, r1.v, 48);
+  }
+  return 0;
+}
+
+// The 68 projective Miller lines (A, B, C) of a G2 point (pairing.h g2_proj_lines, the one-lane
+// form of pair.h g2p_walk_lines): aff = G2A as raw words (x.c0, x.c1, y.c0, y.c1, inf), out =
+// 68 x 3 Fq2 raw.  Returns -1 for the point at infinity.
+int ht_g2_proj_lines_raw(const uint32_t* aff49, uint32_t* out) {
+  static_assert(sizeof(G2A) == 4 * 49, "marshalling layout");
+  G2A Q;
+  memcpy(&Q, aff49, sizeof(G2A));
+  if (Q.inf) return -1;
+  static Fq2 pl[3 * MILLER_STEPS];
+  g2_proj_lines(pl, Q);
+  memcpy(out, pl, sizeof(pl));
+  return 0;
 }
 
 }  // extern "C"

@@ -272,7 +272,7 @@ def sr_call(name, label, square):
 # gen_mul with the column digit added into ACC[k] through the carry chain s[66:67].
 # hbtc_fqredc_sr: r (v8..v19) = ACC * 2^-384 mod p, r < 2p, for ACC < 48 p^2 (ACC unchanged):
 # Montgomery digits q0..q11 over ACC's low half, the quotient (ACC + Q p) / 2^384 < 48 p^2 / 2^384
-# + p < 5.6p (12 words), then conditional subtractions of 4p and 2p.  48 p^2 bounds a sum of 12
+# + p < 5.876p < 6p (12 words), then conditional subtractions of 4p and 2p.  48 p^2 bounds a sum of 12
 # products of reduced operands (< 2p each).
 SR_MACC, SR_CC = 60, 66
 # A second accumulator (v85..v109) with its own pair of subroutines (hbtc_fqmac2_sr,
@@ -349,7 +349,7 @@ def redc_body(base=SR_MACC):
         else:
             out.append("v_mov_b32 %s, %s" % (R(k - 12), lo))
         out.append("v_mov_b32 %s, %s" % (nlo, hi))
-    # r < 2^384: column 23's high word and ACC[24] are 0 for ACC < 48 p^2 (see above).  r < 5.6p:
+    # r < 2^384: column 23's high word and ACC[24] are 0 for ACC < 48 p^2 (see above).  r < 6p:
     # subtract 4p, then 2p, where they fit (r - mp into Q, keep r on a borrow).  The multiple's
     # words go through a VGPR: a literal and the VCC carry-in together exceed the constant bus.
     for m in (4, 2):
