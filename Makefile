@@ -20,7 +20,7 @@ SKG_PARTS := 10
 KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_PARTS),$(BUILD)/hbtc_rlc.p$(p).o) \
          $(foreach p,$(MSM_PARTS),$(BUILD)/hbtc_msm.p$(p).o) $(foreach p,$(SKG_PARTS),$(BUILD)/hbtc_skg.p$(p).o) \
          $(BUILD)/hbtc_check.c1.o $(BUILD)/hbtc_check.c2.o $(BUILD)/hbtc_sig.s1.o $(BUILD)/hbtc_sig.s2.o $(BUILD)/hbtc_pb.o \
-         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o
+         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o
 LIB := hbbft_amd/libhbtc.so
 
 .PHONY: all lib hosttest devtest oracle clean resources roofline-constants
@@ -102,6 +102,11 @@ $(BUILD)/hbtc_pb.o: $(CSRC)/hbtc_pb.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_comb.o: $(CSRC)/hbtc_comb.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
 
+# PublicKey::encrypt (comb u, GLV r pk, pad, lane-pair w) and Fr polynomial evaluation: helpers
+# inlined, the product as the shared subroutine (`make resources-enc` prints the resource report)
+$(BUILD)/hbtc_enc.o: $(CSRC)/hbtc_enc.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
+
 # Reliable Broadcast: Reed-Solomon over GF(2^8), SHA3 Merkle trees and proofs
 $(BUILD)/hbtc_bcast.o: $(CSRC)/hbtc_bcast.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -125,7 +130,14 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=$(PART) -c $(CSRC)/hbtc_kernels.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
 
-hosttest: tests/native/libhbtc_hosttest.so
+.PHONY: resources-enc
+resources-enc:
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
+
+hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so
+tests/native/libhbtc_enc_hosttest.so: tests/native/hbtc_enc_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_enc_hosttest.cpp -o $@
 tests/native/libhbtc_hosttest.so: tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -pthread -I$(CSRC) tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp -o $@
 

@@ -29,6 +29,12 @@ checked against the construction after timing:
       1000 separate copies, so the device work and traffic are those of 1000 Parts), and the
       Ack ciphertexts repeat per distinct (polynomial, sender) value (every Ack is still
       hashed, verified, multiplied and padded on its own).
+  c5p The producing side of c5 at N = --nodes, through hbbft_amd/skg.py as a caller uses it:
+      SyncKeyGen.new (one Part: the commitment, the N rows by hbtc_fr_poly_eval, N row
+      encryptions by hbtc_encrypt, src/sync_key_gen.rs:293-330) and the Acks for --parts valid
+      Parts (N evaluations and N encryptions each, :371-380).  Host buffers and the Python
+      framing are inside the timed region; sampled recipients decrypt their row and values after
+      timing and check them against the commitment and the rows.
 
   bc  Reliable Broadcast of one HoneyBadger epoch at N = 256 (the largest network hbbft's
       reed-solomon-erasure coding accepts: k + p <= 256), one node's view: the N^2 = 65,536 Echo
@@ -39,7 +45,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,bc] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,bc] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -69,7 +75,7 @@ G2_GEN = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bb
                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
 SEED = 0x6862626674
 N_OUT = 6  # output sets rotated per step (bench.py's N_OUT)
-STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "bc": 20}
+STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20}
 
 
 def log(*a):
@@ -710,6 +716,74 @@ def bench_skg(ctx, n, n_parts, n_distinct, steps, warmup, cpu_budget=0.0):
     }
 
 
+def bench_skg_producer(ctx, n, n_parts, steps, warmup):
+    """c5p: one node's SyncKeyGen PRODUCER work at N=n (t = (n-1)/3), through hbbft_amd/skg.py as a
+    caller uses it: SyncKeyGen.new (the Part: commitment, n rows, n row encryptions), then the
+    Acks for n_parts valid Parts (n evaluations and n encryptions each)."""
+    from hbbft_amd import skg, wire
+    rng = random.Random(SEED + 55)
+    t = (n - 1) // 3
+    sks = [rng.randrange(1, R) for _ in range(n)]
+    pk, st = ctx.g1_mul(G1_GEN, fr_bytes(sks))
+    assert not st.any()
+    pub = {i: bytes(pk[48 * i:48 * i + 48]) for i in range(n)}
+    our = 17 % n
+    rows = [[rng.randrange(R) for _ in range(t + 1)] for _ in range(n_parts)]
+    last = {}
+    t_part, t_acks = [0.0], [0.0]
+
+    def step():
+        a0 = time.perf_counter()
+        kg, part = skg.SyncKeyGen.new(ctx, our, sks[our], pub, t)
+        a1 = time.perf_counter()
+        out = [None] * n_parts
+        kg._emit_acks([(p, p % n, rows[p]) for p in range(n_parts)], out)
+        a2 = time.perf_counter()
+        t_part[0] += a1 - a0
+        t_acks[0] += a2 - a1
+        last["part"], last["acks"] = part, out
+
+    for _ in range(warmup):
+        step()
+    t_part[0] = t_acks[0] = 0.0
+    elapsed = timed_steps(ctx, step, steps, 0)
+    per = breakdown(ctx, steps, ["mul", "hash", "enc_g1", "enc_pad", "enc_w", "fr_poly"])
+    # results check against decryption: sampled recipients decrypt their row (checked against the
+    # Part's commitment) and their value of sampled Acks (checked against row(j + 1))
+    part, acks = last["part"], last["acks"]
+    bad = 0
+    sample = sorted(set([0, n - 1] + [rng.randrange(n) for _ in range(6)]))
+    for j in sample:
+        row = skg.decrypt_batch(ctx, sks[j], [part.rows[j]])[0]
+        ok = row is not None
+        if ok:
+            coeffs = wire.poly_from_wire(row)
+            ok = len(coeffs) == t + 1 and int(ctx.skg_check_parts(t, j, part.commit, [coeffs])[0]) == N.ACCEPT
+        bad += 0 if ok else 1
+    for p in sorted(set([0, n_parts - 1] + [rng.randrange(n_parts) for _ in range(2)])):
+        ack = acks[p][1]
+        for j in sample:
+            val = skg.decrypt_batch(ctx, sks[j], [ack.values[j]])[0]
+            ok = val is not None and wire.fr_value_from_wire(val) == skg._poly_eval(rows[p], j + 1)
+            bad += 0 if ok else 1
+    if bad:
+        raise SystemExit("c5p: %d decrypted rows / values differ from the construction" % bad)
+    n_enc = n + n_parts * n
+    return {
+        "metric": "SyncKeyGen producer: encryptions/sec (one Part + the Acks of n_parts Parts)",
+        "value": round(n_enc * steps / elapsed, 1), "unit": "encryptions/s (rows and values evaluated, framed and encrypted)",
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
+        "higher_is_better": True, "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (random bivariate polynomial, random rows); host buffers (PCIe-inclusive), "
+                "Python framing included",
+        "config": {"workload": "c5p: SyncKeyGen N=%d producer: 1 Part (%d commitment points, %d rows) + %d Acks of %d values"
+                   % (n, (t + 1) * (t + 2) // 2, n, n_parts, n), "N": n, "t": t, "parts": n_parts,
+                   "encryptions": n_enc},
+        "part_ms": round(t_part[0] / steps * 1e3, 3), "acks_ms": round(t_acks[0] / steps * 1e3, 3),
+        "kernel_event_spans_ms_per_step": per, "mismatches": bad,
+    }
+
+
 def bench_broadcast(ctx, n, value_bytes, steps, warmup):
     """bc: one node's Reliable Broadcast work for an epoch of n proposers (see the docstring)."""
     from hbbft_amd import broadcast as G
@@ -848,7 +922,8 @@ def main():
     ap.add_argument("--slots", default=None,
                     help="c2 / c4: explicit device slots of the node, e.g. 0,0 (two contexts on GPU 0: "
                          "a rehearsal of the node path on one GPU)")
-    ap.add_argument("--parts", type=int, default=1000, help="c5 Parts")
+    ap.add_argument("--parts", type=int, default=1000, help="c5 / c5p Parts (c5p: at most --nodes)")
+    ap.add_argument("--nodes", type=int, default=1000, help="c5p: N")
     ap.add_argument("--distinct", type=int, default=4, help="c5 distinct bivariate polynomials")
     ap.add_argument("--bc-value", type=int, default=65536, help="bc: bytes per proposed value")
     ap.add_argument("--mode", choices=["rlc", "per_share"], default="rlc")
@@ -867,7 +942,7 @@ def main():
     try:
         for c in args.configs.split(","):
             steps = args.steps if args.steps is not None else STEPS_DEFAULT.get(c, 2)
-            warmup = args.warmup if args.warmup is not None else (1 if c == "c5" else 2)
+            warmup = args.warmup if args.warmup is not None else (1 if c in ("c5", "c5p") else 2)
             if c == "c1":
                 out = bench_c1(ctx, steps, warmup, cpu_budget=0.0 if args.no_cpu else 10.0)
             elif c == "c2":
@@ -879,6 +954,8 @@ def main():
                                   args.corrupt_mode, node=node, cpu_budget=0.0 if args.no_cpu else 10.0)
             elif c == "bc":
                 out = bench_broadcast(ctx, 256, args.bc_value, steps, warmup)
+            elif c == "c5p":
+                out = bench_skg_producer(ctx, args.nodes, min(args.parts, args.nodes), steps, warmup)
             elif c == "c5":
                 out = bench_skg(ctx, 1000, args.parts, args.distinct, steps, warmup,
                                 cpu_budget=0.0 if args.no_cpu else 10.0)

@@ -114,6 +114,8 @@ SIGNATURES = {
     "hbtc_xor_hash_bytes_batch": (_I32, [_U32, _P, _P, _P, _P]),
     "hbtc_commitment_evaluate": (_I32, [_P, _U32, _P, _U32, _P, _P, _P]),
     "hbtc_decrypt": (_I32, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hbtc_encrypt": (_I32, [_P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hbtc_fr_poly_eval": (_I32, [_P, _U32, _U32, _P, _U32, _P, _P]),
     "hbtc_unframe_points_dev": (_I32, [_P, _U32, _U32, _P, _P]),
     "hbtc_stream_wait_ctx": (_I32, [_P, _P]),
     "hbtc_ctx_wait_stream": (_I32, [_P, _P]),
@@ -706,6 +708,55 @@ class Context:
         self._check(self.lib.hbtc_decrypt(self.h, n, _ptr(k), _ptr(u), _ptr(w), _ptr(buf), _ptr(off),
                                           _ptr(out), _ptr(st)), "hbtc_decrypt")
         return [bytes(out[off[i]:off[i + 1]]) if st[i] == ACCEPT else None for i in range(n)], st
+
+    # ---- PublicKey::encrypt
+    def encrypt(self, pks, rs, msgs):
+        """PublicKey::encrypt_with_rng of msgs[i] under pks (one 48-byte key shared by all, or a
+        list) with the scalars rs (ints or packed 32-byte LE): ([(u, v, w)], status); the entries
+        of a key that does not decode are zero-filled (status DECODE_ERR)."""
+        buf, off = _msg_batch(msgs)
+        n = off.size - 1
+        if n == 0:
+            return [], np.zeros(0, np.int32)
+        sc = self._fr_bytes(rs)
+        if sc.size != 32 * n:
+            raise ValueError("one scalar per message")
+        if isinstance(pks, (bytes, bytearray)) and len(pks) == 48:
+            pk, stride = np.frombuffer(bytes(pks), dtype=np.uint8).copy(), 0
+        else:
+            pk, stride = _join(pks, 48), 1
+            if pk.size != 48 * n:
+                raise ValueError("one 48-byte key per message")
+        u, w = np.zeros(48 * n, np.uint8), np.zeros(96 * n, np.uint8)
+        v = np.zeros(max(1, int(off[-1])), np.uint8)
+        st = np.zeros(n, np.int32)
+        self._check(self.lib.hbtc_encrypt(self.h, n, _ptr(pk), stride, _ptr(sc), _ptr(buf), _ptr(off),
+                                          _ptr(u), _ptr(v), _ptr(w), _ptr(st)), "hbtc_encrypt")
+        ub, vb, wb = u.tobytes(), v.tobytes(), w.tobytes()
+        return [(ub[48 * i:48 * i + 48], vb[off[i]:off[i + 1]], wb[96 * i:96 * i + 96])
+                for i in range(n)], st
+
+    # ---- Fr polynomials
+    def fr_poly_eval(self, coeffs, xs):
+        """out[p, j] = sum_k coeffs[p][k] xs[j]^k mod r.  coeffs: a list of equally long rows of
+        ints, or a uint8 array [n_poly, n_coeff, 32] (32-byte LE); xs: ints or uint8 [n_x, 32].
+        Returns uint8 [n_poly, n_x, 32] (canonical 32-byte LE)."""
+        if isinstance(coeffs, np.ndarray):
+            cb = np.ascontiguousarray(coeffs, dtype=np.uint8)
+            n_poly, n_coeff = cb.shape[0], cb.shape[1]
+            cb = cb.reshape(-1)
+        else:
+            n_poly = len(coeffs)
+            n_coeff = len(coeffs[0]) if n_poly else 0
+            if any(len(r) != n_coeff for r in coeffs):
+                raise ValueError("rows of equal length")
+            cb = self._fr_bytes([v for r in coeffs for v in r]) if n_poly * n_coeff else np.zeros(0, np.uint8)
+        xb = self._fr_bytes(xs) if len(xs) else np.zeros(0, np.uint8)
+        n_x = xb.size // 32
+        out = np.zeros(32 * n_poly * n_x, np.uint8)
+        self._check(self.lib.hbtc_fr_poly_eval(self.h, n_poly, n_coeff, _ptr(cb), n_x, _ptr(xb),
+                                               _ptr(out)), "hbtc_fr_poly_eval")
+        return out.reshape(n_poly, n_x, 32)
 
     # ---- commitments
     def commitment_evaluate(self, commit, xs):

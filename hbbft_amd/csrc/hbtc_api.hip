@@ -146,6 +146,8 @@ struct hbtc_ctx {
   // Pippenger combine (HBTC_LAGRANGE_FACT=0: the O(t) per term kernels)
   bool lagrange_fact = true;
   Fr *fact = nullptr, *inv_fact = nullptr;
+  // hbtc_encrypt: the window table of the G1 generator (enc.h, 768 KB), built at the first call
+  EncPt* enc_tab = nullptr;
   std::string ws_suffix;
   hipStream_t stream = nullptr;  // main: items, checks, leaves
   hipStream_t s_prep = nullptr;  // per-instance G2 preparation, overlapped with the item pass
@@ -1631,6 +1633,7 @@ void hbtc_ctx_destroy(hbtc_ctx* c) {
   (void)retire_fence(c);
   (void)reap_retired(c, true);
   if (c->fact) (void)hipFree(c->fact);  // inv_fact lives in the same allocation
+  if (c->enc_tab) (void)hipFree(c->enc_tab);
   if (c->prep.aff) (void)hipFree(c->prep.aff);
   if (c->prep.st) (void)hipFree(c->prep.st);
   if (c->prep.lines) (void)hipFree(c->prep.lines);
@@ -3171,6 +3174,138 @@ int hbtc_decrypt(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t*
     for (size_t j2 = 0; j2 < len; ++j2) o[j2] ^= msgs[offsets[i] + j2];
   });
   return HBTC_OK;
+}
+
+int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_stride,
+                 const uint8_t* r_le32, const uint8_t* msgs, const uint32_t* offsets,
+                 uint8_t* out_u_c48, uint8_t* out_v, uint8_t* out_w_c96, int32_t* status) {
+  if (!c) return HBTC_ERR_ARG;
+  if (n == 0) return HBTC_OK;
+  if (!pk_c48 || pk_stride > 1 || !r_le32 || !offsets || !out_u_c48 || !out_w_c96 || !status ||
+      (offsets[n] && (!msgs || !out_v)) || !hash_offsets_ok(n, offsets))
+    return HBTC_ERR_ARG;
+  Guard g(c);
+  // first block of every item's pad (16 pad bytes per ChaCha block)
+  std::vector<uint32_t> blk(n + 1);
+  uint64_t nb = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    blk[i] = (uint32_t)nb;
+    nb += ((uint64_t)(offsets[i + 1] - offsets[i]) + 15) / 16;
+  }
+  if (nb > 0xffffff00ull) return fail(c, HBTC_ERR_ARG, "encrypt: too many pad blocks in one call");
+  blk[n] = (uint32_t)nb;
+  const size_t total = offsets[n];
+  if (!c->enc_tab) {  // the generator's window table, once per context
+    EncPt* tab = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&tab), ENC_TAB_BYTES) != hipSuccess)
+      return fail(c, HBTC_ERR_OOM, "hipMalloc enc.tab");
+    const hipError_t e = launch_enc_table(c->stream, tab);
+    if (e != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+      (void)hipFree(tab);
+      return fail(c, HBTC_ERR_DEVICE, std::string("enc table: ") + hipGetErrorString(e));
+    }
+    c->enc_tab = tab;  // every lane's stream may read it from here on
+  }
+  const uint32_t n_pk = pk_stride ? n : 1;
+  void *d_pk, *d_r, *d_msgs, *d_off, *d_blk;
+  HB_TRY(upload(c, "enc.pk", pk_c48, (size_t)48 * n_pk, &d_pk));
+  HB_TRY(upload(c, "enc.r", r_le32, (size_t)32 * n, &d_r));
+  HB_TRY(upload(c, "enc.msgs", msgs, total, &d_msgs));
+  HB_TRY(upload(c, "enc.off", offsets, (size_t)4 * (n + 1), &d_off));
+  HB_TRY(upload(c, "enc.blk", blk.data(), (size_t)4 * (n + 1), &d_blk));
+  G1A* d_pkdec;
+  G2A* d_cand;
+  int32_t *d_pkst, *d_st;
+  uint32_t *d_seed, *d_flag;
+  uint8_t *d_u, *d_v, *d_w;
+  HB_TRY(wst(c, "enc.pkdec", n_pk, &d_pkdec));
+  HB_TRY(wst(c, "enc.pkst", n_pk, &d_pkst));
+  HB_TRY(wst(c, "enc.st", n, &d_st));
+  HB_TRY(wst(c, "enc.seed", (size_t)8 * n, &d_seed));
+  HB_TRY(wst(c, "enc.flag", n, &d_flag));
+  HB_TRY(wst(c, "enc.cand", n, &d_cand));
+  HB_TRY(wst(c, "enc.u", (size_t)48 * n, &d_u));
+  HB_TRY(wst(c, "enc.v", total, &d_v));
+  HB_TRY(wst(c, "enc.w", (size_t)96 * n, &d_w));
+  HB_TRY(timed(c, "enc_g1", [&] {
+    const hipError_t e = launch_g1_decode(c->stream, (const uint8_t*)d_pk, n_pk, d_pkdec, d_pkst);
+    if (e != hipSuccess) return e;
+    return launch_enc_g1(c->stream, n, d_pkdec, d_pkst, pk_stride, (const uint8_t*)d_r, c->enc_tab, d_u,
+                         d_seed, d_st);
+  }));
+  HB_TRY(timed(c, "enc_pad", [&] {
+    return launch_enc_pad(c->stream, n, (uint32_t)nb, (const uint32_t*)d_blk, (const uint32_t*)d_off,
+                          d_seed, d_st, (const uint8_t*)d_msgs, d_v);
+  }));
+  HB_TRY(timed(c, "hash", [&] {
+    return launch_hash_cand(c->stream, n, d_u, d_v, (const uint32_t*)d_off, d_cand);
+  }));
+  HB_TRY(timed(c, "enc_w", [&] {
+    return launch_enc_w(c->stream, n, d_cand, (const uint8_t*)d_r, d_st, d_w, d_flag);
+  }));
+  std::vector<uint32_t> flag(n);
+  HB_TRY(download(c, out_u_c48, d_u, (size_t)48 * n));
+  HB_TRY(download(c, out_v, d_v, total));
+  HB_TRY(download(c, out_w_c96, d_w, (size_t)96 * n));
+  HB_TRY(download(c, status, d_st, (size_t)4 * n));
+  HB_TRY(download(c, flag.data(), d_flag, (size_t)4 * n));
+  HB_TRY(sync(c));
+  // [h2] cand = O (probability ~2^-250, never observed): G2::rand draws again; the host hash
+  // continues the loop exactly, and the generic multiplication finishes those items
+  std::vector<uint32_t> redo;
+  for (uint32_t i = 0; i < n; ++i)
+    if (status[i] == HBTC_ACCEPT && flag[i]) redo.push_back(i);
+  if (!redo.empty()) {
+    const uint32_t m = (uint32_t)redo.size();
+    std::vector<uint8_t> H((size_t)96 * m), k((size_t)32 * m), w((size_t)96 * m);
+    std::vector<int32_t> st(m);
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t i = redo[j];
+      hash_g1_g2_c96(out_u_c48 + 48 * (size_t)i, out_v + offsets[i], offsets[i + 1] - offsets[i],
+                     H.data() + 96 * (size_t)j);
+      memcpy(k.data() + 32 * (size_t)j, r_le32 + 32 * (size_t)i, 32);
+    }
+    HB_TRY(point_mul_host(c, 2, m, H.data(), 1, k.data(), w.data(), st.data()));
+    for (uint32_t j = 0; j < m; ++j) {
+      if (st[j] != HBTC_ACCEPT) return fail(c, HBTC_ERR_DEVICE, "encrypt: the hash point failed to decode");
+      memcpy(out_w_c96 + 96 * (size_t)redo[j], w.data() + 96 * (size_t)j, 96);
+    }
+  }
+  return HBTC_OK;
+}
+
+int hbtc_fr_poly_eval(hbtc_ctx* c, uint32_t n_poly, uint32_t n_coeff, const uint8_t* coeffs_le32,
+                      uint32_t n_x, const uint8_t* x_le32, uint8_t* out_le32) {
+  if (!c) return HBTC_ERR_ARG;
+  const uint64_t n_out = (uint64_t)n_poly * n_x;
+  if (n_out == 0) return HBTC_OK;
+  if (!out_le32) return HBTC_ERR_ARG;
+  if (n_coeff == 0) {
+    memset(out_le32, 0, (size_t)n_out * 32);
+    return HBTC_OK;
+  }
+  const uint64_t n_c = (uint64_t)n_poly * n_coeff;
+  if (!coeffs_le32 || !x_le32) return HBTC_ERR_ARG;
+  Guard g(c);
+  if (n_c > (1ull << 31) || n_out > (1ull << 31))
+    return fail(c, HBTC_ERR_ARG, "fr_poly_eval: more than 2^31 coefficients or outputs in one call");
+  void *d_c, *d_x;
+  Fr *d_cm, *d_xm;
+  uint8_t* d_out;
+  HB_TRY(upload(c, "frp.c", coeffs_le32, (size_t)n_c * 32, &d_c));
+  HB_TRY(upload(c, "frp.x", x_le32, (size_t)n_x * 32, &d_x));
+  HB_TRY(wst(c, "frp.cm", (size_t)n_c, &d_cm));
+  HB_TRY(wst(c, "frp.xm", (size_t)n_x, &d_xm));
+  HB_TRY(wst(c, "frp.out", (size_t)n_out * 32, &d_out));
+  HB_TRY(timed(c, "fr_poly", [&] {
+    hipError_t e = launch_fr_to_mont(c->stream, n_c, (const uint8_t*)d_c, d_cm);
+    if (e != hipSuccess) return e;
+    e = launch_fr_to_mont(c->stream, n_x, (const uint8_t*)d_x, d_xm);
+    if (e != hipSuccess) return e;
+    return launch_fr_poly_eval(c->stream, n_poly, n_coeff, d_cm, n_x, d_xm, d_out);
+  }));
+  HB_TRY(download(c, out_le32, d_out, (size_t)n_out * 32));
+  return sync(c);
 }
 
 }  // extern "C"

@@ -351,6 +351,27 @@ hipError_t launch_skg_ack_rows(hipStream_t s, uint32_t n_acks, uint32_t t1, cons
                                const uint32_t* ack_part, const uint32_t* ack_sender,
                                const Fr* vals, int32_t* status);
 
+// ---- PublicKey::encrypt and Fr polynomial evaluation (hbtc_enc.hip, arithmetic in enc.h)
+struct EncPt;  // enc.h: one affine entry of the generator's window table
+constexpr size_t ENC_TAB_BYTES = (size_t)32 * 256 * 2 * sizeof(Fq);
+hipError_t launch_enc_table(hipStream_t s, EncPt* tab);
+// u = r G1 (compressed), seeds = the 8 ChaCha seed words of hash_bytes(r pk, .), status = ACCEPT /
+// DECODE_ERR from pk_st (launch_g1_decode's); pk_stride 0: one key for every item
+hipError_t launch_enc_g1(hipStream_t s, uint32_t n, const G1A* pk, const int32_t* pk_st,
+                         uint32_t pk_stride, const uint8_t* r_le32, const EncPt* tab, uint8_t* out_u,
+                         uint32_t* seeds, int32_t* status);
+// v = msg XOR pad, one lane per 16-byte pad block; blk_off: n + 1 first-block indices
+hipError_t launch_enc_pad(hipStream_t s, uint32_t n, uint32_t n_blocks, const uint32_t* blk_off,
+                          const uint32_t* offsets, const uint32_t* seeds, const int32_t* status,
+                          const uint8_t* msgs, uint8_t* out_v);
+// w = [r] [h2] cand (compressed) on lane pairs; flag[i] = 1: [h2] cand = O, the host finishes it
+hipError_t launch_enc_w(hipStream_t s, uint32_t n, const G2A* cand, const uint8_t* r_le32,
+                        const int32_t* status, uint8_t* out_w, uint32_t* flag);
+// n 256-bit little-endian values -> Montgomery Fr of their residues
+hipError_t launch_fr_to_mont(hipStream_t s, uint64_t n, const uint8_t* in_le32, Fr* out);
+// out[p * n_x + j] = poly_p(x_j), canonical; coeffs / xs in Montgomery form
+hipError_t launch_fr_poly_eval(hipStream_t s, uint32_t n_poly, uint32_t n_coeff, const Fr* coeffs,
+                               uint32_t n_x, const Fr* xs, uint8_t* out_le32);
 
 // ---- Reliable Broadcast (hbtc_bcast.hip)
 hipError_t launch_gf_apply(hipStream_t s, uint32_t n_jobs, const uint32_t* jobs, uint8_t* shards,

@@ -55,24 +55,33 @@ def _fr_le(vals):
 # ------------------------------------------------------------------------------ encryption
 def encrypt_batch(ctx, pks, msgs, rs=None):
     """PublicKey::encrypt_with_rng for n (pk_i, msg_i): u = r G1, v = msg XOR hash_bytes(r pk),
-    w = r hash_g1_g2(u, v).  The group work runs batched on the GPU, the pads on the host."""
+    w = r hash_g1_g2(u, v), in one hbtc_encrypt call (device-resident between its stages)."""
     n = len(msgs)
     if n == 0:
         return []
     rs = rs or [secrets.randbelow(R - 1) + 1 for _ in range(n)]
-    sc = _fr_le(rs)
-    u, st1 = ctx.g1_mul(G1_GEN, sc)
-    g, st2 = ctx.g1_mul([bytes(p) for p in pks], sc)
-    if st1.any() or st2.any():
+    cts, st = ctx.encrypt([bytes(p) for p in pks], rs, msgs)
+    if st.any():
         raise N.HbtcError("encrypt: a public key failed to decode")
-    us = [bytes(u[48 * i:48 * i + 48]) for i in range(n)]
-    gs = [bytes(g[48 * i:48 * i + 48]) for i in range(n)]
-    vs = N.xor_hash_bytes_batch(gs, msgs)
-    H = ctx.hash_g1_g2_batch(us, vs)
-    w, st3 = ctx.g2_mul(H, sc)
-    if st3.any():
-        raise N.HbtcError("encrypt: hash point failed to decode")
-    return [Ciphertext(us[i], vs[i], bytes(w[96 * i:96 * i + 96])) for i in range(n)]
+    return [Ciphertext(u, v, w) for u, v, w in cts]
+
+
+def bivar_rows(ctx, b, t, n):
+    """The wire-framed rows 1..n of the symmetric bivariate polynomial b (packed, coeff_pos
+    order): row_x coefficient k = poly_k(x) with poly_k = b[k, .], one hbtc_fr_poly_eval call
+    (_bivar_row is the Python-integer form of one row)."""
+    polys = [[b[coeff_pos(k, j)] for j in range(t + 1)] for k in range(t + 1)]
+    out = ctx.fr_poly_eval(polys, list(range(1, n + 1)))  # [k, x, 32]
+    return wire.polys_to_wire(np.ascontiguousarray(out.transpose(1, 0, 2)))
+
+
+def ack_values(ctx, rows, n):
+    """Per verified row the wire-framed values row(1) .. row(n) of its Ack, one
+    hbtc_fr_poly_eval call for all rows (_poly_eval is the Python-integer form of one value)."""
+    if not rows:
+        return []
+    out = ctx.fr_poly_eval([list(r) for r in rows], list(range(1, n + 1)))  # [row, x, 32]
+    return [wire.frs_to_wire(out[a]) for a in range(len(rows))]
 
 
 def decrypt_batch(ctx, sk, cts):
@@ -126,7 +135,7 @@ class SyncKeyGen:
         if st.any():
             raise N.HbtcError("commitment failed")
         commit = [bytes(cm[48 * i:48 * i + 48]) for i in range(len(b))]
-        rows = [wire.poly_to_wire(_bivar_row(b, t, i + 1)) for i in range(len(kg.ids))]
+        rows = bivar_rows(ctx, b, t, len(kg.ids))
         cts = encrypt_batch(ctx, [kg.pub_keys[n] for n in kg.ids], rows)
         return kg, Part(commit, cts)
 
@@ -274,11 +283,8 @@ class SyncKeyGen:
         if not new_acks:
             return
         n = len(self.ids)
-        msgs, pks = [], []
-        for _, _, row in new_acks:
-            for i in range(n):
-                msgs.append(wire.fr_to_wire(_poly_eval(row, i + 1)))
-                pks.append(self.pub_keys[self.ids[i]])
+        msgs = [m for vals in ack_values(self.ctx, [row for _, _, row in new_acks], n) for m in vals]
+        pks = [self.pub_keys[self.ids[i]] for i in range(n)] * len(new_acks)
         cts = encrypt_batch(self.ctx, pks, msgs)
         for a, (m, s_idx, _) in enumerate(new_acks):
             out[m] = ("valid", Ack(s_idx, cts[a * n:(a + 1) * n]))

@@ -80,3 +80,29 @@ def poly_from_wire(b):
         v, pos = fr_from_wire(b, pos)
         out.append(v)
     return out
+
+
+# ---- numpy framing of device results (hbtc_fr_poly_eval: canonical 32-byte little-endian values)
+def _framed(le32):
+    """uint8 [..., 32] little-endian canonical scalars -> uint8 [..., 40] FieldWraps."""
+    import numpy as np
+    a = np.ascontiguousarray(le32, dtype=np.uint8)
+    if a.shape[-1] != 32:
+        raise ValueError("32-byte scalars expected")
+    out = np.zeros(a.shape[:-1] + (40,), np.uint8)
+    out[..., 0] = 32
+    out[..., 8:] = a[..., ::-1]
+    return out
+
+
+def frs_to_wire(le32):
+    """[n, 32] -> n FieldWrap messages (fr_to_wire of every value)."""
+    f = _framed(le32)
+    return [f[i].tobytes() for i in range(f.shape[0])]
+
+
+def polys_to_wire(le32):
+    """[n_rows, n_coeff, 32] -> n_rows Poly messages (poly_to_wire of every row)."""
+    f = _framed(le32)
+    head = struct.pack("<Q", f.shape[1])
+    return [head + f[i].tobytes() for i in range(f.shape[0])]

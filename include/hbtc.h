@@ -22,6 +22,9 @@
  *                                                                             src/sync_key_gen.rs:366
  *   hbtc_skg_check_acks      SyncKeyGen::handle_ack_or_err: commit.evaluate(x, y) == val * G1
  *                                                                             src/sync_key_gen.rs:493
+ *   hbtc_encrypt             PublicKey::encrypt_with_rng (HoneyBadger::propose src/honey_badger/honey_badger.rs:98-114,
+ *                            Part rows and Ack values src/sync_key_gen.rs:320-322,372-379)
+ *   hbtc_fr_poly_eval        BivarPoly::row / Poly::evaluate over Fr (src/sync_key_gen.rs:320,374)
  *   hbtc_g1_msm/hbtc_g2_msm  batched Pippenger MSMs (BivarCommitment::row / Commitment::evaluate,
  *                            src/sync_key_gen.rs:345,366,493); the combines run on the same kernels
  *
@@ -177,6 +180,28 @@ int hbtc_decrypt(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const uint8_
 /* Ciphertext::verify: e(G1, w_i) == e(u_i, H_i) with H_i = hash_g1_g2(u_i, v_i). */
 int hbtc_verify_ciphertexts(hbtc_ctx* ctx, uint32_t n, const uint8_t* u_c48,
                             const uint8_t* H_c96, const uint8_t* w_c96, int32_t* status);
+
+/* PublicKey::encrypt_with_rng for n items: u_i = r_i G1, v_i = msg_i XOR hash_bytes(r_i pk_i, |msg_i|),
+ * w_i = r_i hash_g1_g2(u_i, v_i): HoneyBadger::propose (src/honey_badger/honey_badger.rs:98-114),
+ * every row of a SyncKeyGen Part (src/sync_key_gen.rs:320-322) and every value of an Ack
+ * (src/sync_key_gen.rs:372-379; 10^6 per era at N = 1000).  One call, device-resident between its
+ * stages (DESIGN.md "Encryption"): inputs uploaded once, outputs downloaded once, one wait at the
+ * end.  pk_stride is 1 for one key per item or 0 for one shared key; r: 32-byte little-endian,
+ * any value < 2^256, taken mod the group order; msg_i = msgs[offsets[i] .. offsets[i+1]); out_v
+ * has the same layout.  status[i] = ACCEPT or DECODE_ERR (pk_i does not decode: exactly the items
+ * hbtc_g1_mul rejects for the same bytes); the outputs of a DECODE_ERR item are zero-filled.
+ * r == 0 mod the order yields u = w = the point at infinity, as the reference's arithmetic does. */
+int hbtc_encrypt(hbtc_ctx* ctx, uint32_t n, const uint8_t* pk_c48, uint32_t pk_stride,
+                 const uint8_t* r_le32, const uint8_t* msgs, const uint32_t* offsets,
+                 uint8_t* out_u_c48, uint8_t* out_v, uint8_t* out_w_c96, int32_t* status);
+
+/* out[p * n_x + j] = sum_k coeffs[p][k] * x_j^k mod r (canonical 32-byte LE).  coeffs: n_poly rows of
+ * n_coeff 32-byte LE values, x: n_x 32-byte LE values, all taken mod r.  n_coeff == 0 gives zeros.
+ * The scalar half of SyncKeyGen: the rows of the bivariate polynomial (row_i coefficient k =
+ * poly_k(i + 1): n_poly = t + 1, n_x = N; src/sync_key_gen.rs:320) and the Ack values
+ * row(i + 1) (n_poly = 1 per Part, n_x = N; src/sync_key_gen.rs:372-379). */
+int hbtc_fr_poly_eval(hbtc_ctx* ctx, uint32_t n_poly, uint32_t n_coeff, const uint8_t* coeffs_le32,
+                      uint32_t n_x, const uint8_t* x_le32, uint8_t* out_le32);
 
 /* ---- host hashes (no context, no GPU) ----------------------------------------------------- */
 /* threshold_crypto's crate-internal hash_g2(msg) -> compressed G2 (96 B), and hash_g1_g2(g1, msg)

@@ -11,6 +11,7 @@
 //!   ThresholdDecryption -> verify_decryption_share        verify_dec_shares   (src/threshold_decryption.rs:159)
 //!   ThresholdDecryption -> PublicKeySet::decrypt          combine_dec         (src/threshold_decryption.rs:181-185)
 //!   SyncKeyGen::handle_part / handle_ack                  skg_check_parts / skg_check_acks / decrypt
+//!   HoneyBadger::propose, SyncKeyGen::new / Ack values     encrypt / fr_poly_eval (src/sync_key_gen.rs:320-322,372-379)
 #![allow(clippy::too_many_arguments)]
 pub mod ffi;
 #[cfg(feature = "experimental-queues")]
@@ -247,6 +248,40 @@ impl Context {
                               offsets.as_ptr(), out.as_mut_ptr(), st.as_mut_ptr())
         })?;
         Ok((out, st))
+    }
+
+    /// PublicKey::encrypt_with_rng for a batch: (u, v in the msgs layout, w, status).  pk_c48 holds
+    /// one key per item, or a single key shared by all (48 bytes).
+    pub fn encrypt(&self, pk_c48: &[u8], r_le32: &[u8], msgs: &[u8], offsets: &[u32])
+        -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<i32>)> {
+        assert!(!offsets.is_empty() && offsets[0] == 0, "offsets[0] must be 0");
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]), "offsets must be non-decreasing");
+        let n = offsets.len() - 1;
+        assert!(offsets[n] as usize <= msgs.len(), "offsets past the message bytes");
+        assert_eq!(r_le32.len(), 32 * n, "one 32-byte scalar per item");
+        assert!(pk_c48.len() == 48 * n || pk_c48.len() == 48, "one key per item, or one shared key");
+        let stride = if pk_c48.len() == 48 * n { 1 } else { 0 };
+        let (mut u, mut v, mut w, mut st) = (vec![0u8; 48 * n], vec![0u8; msgs.len()], vec![0u8; 96 * n], vec![0i32; n]);
+        self.ok(unsafe {
+            ffi::hbtc_encrypt(self.raw, n as u32, pk_c48.as_ptr(), stride, r_le32.as_ptr(), msgs.as_ptr(),
+                              offsets.as_ptr(), u.as_mut_ptr(), v.as_mut_ptr(), w.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        Ok((u, v, w, st))
+    }
+
+    /// out[p * n_x + j] = poly_p(x_j) over Fr (32-byte LE each): n_poly rows of n_coeff coefficients.
+    pub fn fr_poly_eval(&self, n_coeff: u32, coeffs_le32: &[u8], x_le32: &[u8]) -> Result<Vec<u8>> {
+        assert_eq!(x_le32.len() % 32, 0);
+        let n_x = x_le32.len() / 32;
+        let row = 32 * n_coeff as usize;
+        assert!(row > 0 && coeffs_le32.len() % row == 0, "n_coeff coefficients per polynomial");
+        let n_poly = coeffs_le32.len() / row;
+        let mut out = vec![0u8; 32 * n_poly * n_x];
+        self.ok(unsafe {
+            ffi::hbtc_fr_poly_eval(self.raw, n_poly as u32, n_coeff, coeffs_le32.as_ptr(), n_x as u32,
+                                   x_le32.as_ptr(), out.as_mut_ptr())
+        })?;
+        Ok(out)
     }
 }
 
