@@ -135,9 +135,18 @@ resources-enc:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
 
-hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so
+hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so
+tests/native/libhbtc_dec_hosttest.so: tests/native/hbtc_dec_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_dec_hosttest.cpp -o $@
 tests/native/libhbtc_enc_hosttest.so: tests/native/hbtc_enc_hosttest.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_enc_hosttest.cpp -o $@
+# the decryption pad's host build (k_dec_seed + k_enc_pad bodies) as a stand-alone program under
+# AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-dec
+sanitize-dec: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_dec_host_main.cpp tests/native/hbtc_dec_hosttest.cpp -o $(BUILD)/dec_host_asan
+	$(BUILD)/dec_host_asan
 tests/native/libhbtc_hosttest.so: tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -pthread -I$(CSRC) tests/native/hbtc_hosttest.cpp tests/native/gt_sim.cpp -o $@
 

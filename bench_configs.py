@@ -35,6 +35,13 @@ checked against the construction after timing:
       Parts (N evaluations and N encryptions each, :371-380).  Host buffers and the Python
       framing are inside the timed region; sampled recipients decrypt their row and values after
       timing and check them against the commitment and the rows.
+  td  One ThresholdDecryption epoch to the PLAINTEXT, C3-shaped (N = --nodes, N ciphertexts,
+      t = f + 1; 10^6 shares at N = 1000), contributions of --td-bytes each (not in the default
+      list).  Three paths over the same host inputs, interleaved per repeat: (a)
+      hbtc_threshold_decrypt (shares -> statuses -> g -> plaintext on the device), (b) the composed
+      calls: verify_dec_shares + combine_dec over the verified shares + xor_hash_bytes_batch on
+      the host's cores, (c) the xor_hash_bytes_batch step of (b) alone.  (a) and (b) must give
+      bit-equal plaintexts.  Reports median / minimum per path and the dec_pad kernel span.
 
   bc  Reliable Broadcast of one HoneyBadger epoch at N = 256 (the largest network hbbft's
       reed-solomon-erasure coding accepts: k + p <= 256), one node's view: the N^2 = 65,536 Echo
@@ -45,7 +52,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,bc] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,bc,td] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -75,7 +82,7 @@ G2_GEN = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bb
                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
 SEED = 0x6862626674
 N_OUT = 6  # output sets rotated per step (bench.py's N_OUT)
-STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20}
+STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5}
 
 
 def log(*a):
@@ -784,6 +791,90 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
     }
 
 
+def bench_threshold_decrypt(ctx, n, v_bytes, steps, warmup, corrupt):
+    """td: one ThresholdDecryption epoch to the plaintext (see the docstring): n ciphertexts of
+    v_bytes, n shares each (a fraction `corrupt` wrong), t = f + 1."""
+    rng = random.Random(SEED + 77)
+    nrng = np.random.default_rng(SEED + 77)
+    _, sks = key_shares(rng, n)
+    t = (n - 1) // 3 + 1
+    pk, st = ctx.g1_mul(G1_GEN, fr_bytes(sks))
+    assert not st.any()
+    ks, _ = ctx.keyset_load(pk)
+    # ciphertext k: H = h_k G2, w = r_k h_k G2, share_i = sk_i r_k G1 (e(share, H) == e(pk_i, w))
+    rs = [rng.randrange(1, R) for _ in range(n)]
+    hs = [rng.randrange(1, R) for _ in range(n)]
+    H, _ = ctx.g2_mul(G2_GEN, fr_bytes(hs))
+    w, _ = ctx.g2_mul(G2_GEN, fr_bytes([r * h % R for r, h in zip(rs, hs)]))
+    scal = [sk * r % R for r in rs for sk in sks]
+    for j in rng.sample(range(n * n), int(n * n * corrupt)):
+        scal[j] = (scal[j] + 1) % R
+    shares, st = ctx.g1_mul(G1_GEN, fr_bytes(scal))
+    assert not st.any()
+    del scal
+    idx = np.tile(np.arange(n, dtype=np.uint32), n)
+    off = np.arange(n + 1, dtype=np.uint32) * n
+    vs = [nrng.integers(0, 256, v_bytes, dtype=np.uint8).tobytes() for _ in range(n)]
+    sh = np.asarray(shares, np.uint8).reshape(-1, 48)
+    last = {}
+
+    def path_a():
+        last["a"] = ctx.threshold_decrypt(ks, H, w, None, idx, shares, t, vs, offsets=off)
+
+    def pad_c():
+        g, cst = last["g"]
+        last["b"] = [p if c == N.ACCEPT else None for p, c in zip(N.xor_hash_bytes_batch(g, vs), cst)]
+
+    def path_b():
+        st_b = ctx.verify_dec_shares(ks, H, w, None, idx, shares, offsets=off)
+        ok = (st_b == N.ACCEPT).reshape(n, n)
+        first = [np.flatnonzero(ok[k])[:t] + k * n for k in range(n)]  # the verified shares kept
+        flat = np.concatenate(first)
+        last["g"] = ctx.combine_dec([len(f) for f in first], idx[flat], sh[flat].reshape(-1), t)
+        pad_c()
+
+    for _ in range(warmup):
+        path_a()
+        path_b()
+    times = {"a": [], "b": [], "c": []}
+    for _ in range(steps):  # interleaved: every repeat runs the three paths back to back
+        for name, fn in (("a", path_a), ("b", path_b), ("c", pad_c)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    plain_a = last["a"][1]
+    if plain_a != last["b"]:
+        bad = sum(1 for x, y in zip(plain_a, last["b"]) if x != y)
+        raise SystemExit("td: %d plaintexts of hbtc_threshold_decrypt differ from the composed path" % bad)
+    if not all(p is not None for p in plain_a):
+        raise SystemExit("td: a ciphertext did not combine")
+    # the seed + pad kernels' span, from one more call with event timing on
+    ctx.timing_enable(True)
+    ctx.timing_reset()
+    path_a()
+    span, launches = ctx.timing_read("dec_pad")
+    ctx.timing_enable(False)
+
+    def stat(xs):
+        return {"median_ms": round(float(np.median(xs)), 3), "min_ms": round(min(xs), 3),
+                "max_ms": round(max(xs), 3)}
+
+    return {
+        "metric": "ThresholdDecryption epoch to the plaintext: ms per epoch, hbtc_threshold_decrypt",
+        "value": stat(times["a"])["median_ms"], "unit": "ms per epoch (median of %d interleaved repeats)" % steps,
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "higher_is_better": False,
+        "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (random key shares, ciphertexts, shares with %.1f %% wrong); host buffers "
+                "(PCIe-inclusive), Python list handling included" % (100 * corrupt),
+        "config": {"workload": "td: N=%d, %d ciphertexts of %d bytes, %d shares, t=%d"
+                   % (n, n, v_bytes, n * n, t), "N": n, "t": t, "v_bytes": v_bytes, "shares": n * n},
+        "a_threshold_decrypt": stat(times["a"]), "b_composed": stat(times["b"]),
+        "c_xor_hash_bytes_batch": stat(times["c"]),
+        "dec_pad_span_ms": round(span, 3), "dec_pad_launches": int(launches),
+        "plaintexts_bit_equal": True,
+    }
+
+
 def bench_broadcast(ctx, n, value_bytes, steps, warmup):
     """bc: one node's Reliable Broadcast work for an epoch of n proposers (see the docstring)."""
     from hbbft_amd import broadcast as G
@@ -923,8 +1014,9 @@ def main():
                     help="c2 / c4: explicit device slots of the node, e.g. 0,0 (two contexts on GPU 0: "
                          "a rehearsal of the node path on one GPU)")
     ap.add_argument("--parts", type=int, default=1000, help="c5 / c5p Parts (c5p: at most --nodes)")
-    ap.add_argument("--nodes", type=int, default=1000, help="c5p: N")
+    ap.add_argument("--nodes", type=int, default=1000, help="c5p / td: N")
     ap.add_argument("--distinct", type=int, default=4, help="c5 distinct bivariate polynomials")
+    ap.add_argument("--td-bytes", type=int, default=1024, help="td: bytes per contribution")
     ap.add_argument("--bc-value", type=int, default=65536, help="bc: bytes per proposed value")
     ap.add_argument("--mode", choices=["rlc", "per_share"], default="rlc")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
@@ -954,6 +1046,8 @@ def main():
                                   args.corrupt_mode, node=node, cpu_budget=0.0 if args.no_cpu else 10.0)
             elif c == "bc":
                 out = bench_broadcast(ctx, 256, args.bc_value, steps, warmup)
+            elif c == "td":
+                out = bench_threshold_decrypt(ctx, args.nodes, args.td_bytes, steps, warmup, args.corrupt)
             elif c == "c5p":
                 out = bench_skg_producer(ctx, args.nodes, min(args.parts, args.nodes), steps, warmup)
             elif c == "c5":

@@ -61,6 +61,10 @@ SIGNATURES = {
     "hbtc_combine_sigs": (_I32, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P]),
     "hbtc_verify_dec_shares": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "hbtc_combine_dec": (_I32, [_P, _U32, _P, _P, _P, _U32, _P, _P]),
+    "hbtc_threshold_decrypt": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
+    "hbtc_pad_xor_dev": (_I32, [_P, _U32, _P, _P, _P, _P, _P]),
+    "hbtc_dec_epoch_submit_plain": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P,
+                                           _P]),
     "hbtc_verify_ciphertexts": (_I32, [_P, _U32, _P, _P, _P, _P]),
     "hbtc_g1_mul": (_I32, [_P, _U32, _P, _U32, _P, _P, _P]),
     "hbtc_g2_mul": (_I32, [_P, _U32, _P, _U32, _P, _P, _P]),
@@ -503,6 +507,27 @@ class Context:
                                                    ctypes.byref(tk)), "hbtc_dec_epoch_submit")
         return self._hold(tk.value, outs, (off,))
 
+    def dec_epoch_submit_plain(self, keyset, H, w, offsets, idx, shares, t, vs):
+        """dec_epoch_submit plus the plaintexts (hbtc.h hbtc_dec_epoch_submit_plain; t >= 1): vs is
+        one v per ciphertext.  wait() gives (status, g [n_ct, 48], combine status, plain, v_offsets):
+        ciphertext k's plaintext is plain[v_offsets[k]:v_offsets[k + 1]], zeros where its combine
+        status is not ACCEPT."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_ct, n = off.size - 1, int(off[-1])
+        Hb, wb, sb = _join(H, 96), _join(w, 96), _join(shares, 48)
+        ix = np.ascontiguousarray(idx, dtype=np.uint32)
+        vb, voff = _msg_batch(vs)
+        if voff.size - 1 != n_ct:
+            raise ValueError("one v per ciphertext")
+        outs = (np.empty(max(n, 1), np.int32), np.empty((max(n_ct, 1), 48), np.uint8),
+                np.empty(max(n_ct, 1), np.int32), np.zeros(max(int(voff[-1]), 1), np.uint8), voff)
+        tk = ctypes.c_uint64()
+        self._check(self.lib.hbtc_dec_epoch_submit_plain(
+            self.h, keyset, n_ct, _ptr(Hb), _ptr(wb), _ptr(off), _ptr(ix), _ptr(sb), t, _ptr(vb), _ptr(voff),
+            _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[3]), _ptr(outs[2]), ctypes.byref(tk)),
+            "hbtc_dec_epoch_submit_plain")
+        return self._hold(tk.value, outs, (off,))
+
     def sig_epoch_submit(self, keyset, H, offsets, idx, sigs, t, outs=None):
         """The SignatureShare epoch (coins): wait() gives (status, sig [n, 96], parity, combine status)."""
         off = np.ascontiguousarray(offsets, dtype=np.uint32)
@@ -557,6 +582,36 @@ class Context:
         self._check(self.lib.hbtc_combine_dec(self.h, n, _ptr(off), _ptr(ix), _ptr(sb), t,
                                               _ptr(out), _ptr(st)), "hbtc_combine_dec")
         return [bytes(out[48 * k:48 * k + 48]) for k in range(n)], st
+
+    def threshold_decrypt(self, keyset, H, w, counts, idx, shares, t, vs, offsets=None):
+        """One ThresholdDecryption round (hbtc.h hbtc_threshold_decrypt): every share verified, the
+        first t ACCEPTed shares of each ciphertext combined, and the plaintext v XOR hash_bytes(g)
+        made on the GPU.  vs: one v per ciphertext.  Returns (status, plaintexts, g, inst_status);
+        plaintexts[k] is bytes, or None where inst_status[k] is not ACCEPT (g[k] is zeros then)."""
+        off = _offsets(offsets if offsets is not None else counts, offsets is not None)
+        n_ct = off.size - 1
+        Hb, wb, sb = _join(H, 96), _join(w, 96), _join(shares, 48)
+        ix = np.ascontiguousarray(idx, dtype=np.uint32)
+        vb, voff = _msg_batch(vs)
+        if voff.size - 1 != n_ct:
+            raise ValueError("one v per ciphertext")
+        st = np.empty(int(off[-1]), dtype=np.int32)
+        g = np.zeros(48 * n_ct, np.uint8)
+        cst = np.empty(n_ct, np.int32)
+        plain = np.zeros(max(int(voff[-1]), 1), np.uint8)
+        self._check(self.lib.hbtc_threshold_decrypt(
+            self.h, keyset, n_ct, _ptr(Hb), _ptr(wb), _ptr(off), _ptr(ix), _ptr(sb), t, _ptr(vb), _ptr(voff),
+            _ptr(st), _ptr(g), _ptr(plain), _ptr(cst)), "hbtc_threshold_decrypt")
+        pts = [bytes(plain[voff[k]:voff[k + 1]]) if cst[k] == 0 else None for k in range(n_ct)]
+        return st, pts, [bytes(g[48 * k:48 * k + 48]) for k in range(n_ct)], cst
+
+    def pad_xor(self, d_g, d_gate, v_offsets, d_v, d_out):
+        """hbtc.h hbtc_pad_xor_dev: d_out = d_v XOR hash_bytes(g_k, .) per item on device pointers
+        (dev_alloc), behind any pending combine that writes d_g / d_gate (None: no gate);
+        v_offsets is a host array.  sync() / dev_download before reading d_out."""
+        voff = np.ascontiguousarray(v_offsets, dtype=np.uint32)
+        self._check(self.lib.hbtc_pad_xor_dev(self.h, voff.size - 1, d_g, d_gate, _ptr(voff), d_v, d_out),
+                    "hbtc_pad_xor_dev")
 
     # ---- scalar multiplication
     def _mul(self, fn, size, bases, scalars):

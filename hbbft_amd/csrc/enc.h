@@ -226,11 +226,22 @@ HD void enc_to_aff2(G1A& a, G1A& b, const G1J& p, const G1J& q) {
 // The ChaCha seed of hash_bytes(g, .): sha3_256 of the 48 compressed bytes (12 words as the
 // codec stores them, little-endian in memory).
 HASH_HD void enc_pad_seed(uint32_t seed[8], const uint32_t g_words[12]) {
-  uint8_t b[48], d[32];
-  for (int i = 0; i < 12; ++i)
-    for (int j = 0; j < 4; ++j) b[4 * i + j] = (uint8_t)(g_words[i] >> (8 * j));
-  sha3_256(b, 48, d);
-  seed_of_digest(d, seed);
+  // the one-block sponge written out on whole lanes (no byte buffers, so no scratch on the GPU):
+  // 48 message bytes = lanes 0..5, the 0x06 pad byte at position 48, 0x80 at position 135
+  uint64_t a[25];
+#pragma unroll
+  for (int i = 0; i < 25; ++i) a[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) a[i] = (uint64_t)g_words[2 * i] | ((uint64_t)g_words[2 * i + 1] << 32);
+  a[6] = 0x06ull;
+  a[16] = 0x80ull << 56;
+  keccak_f(a);
+  // seed_of_digest: seed word i = the digest bytes 4 i .. 4 i + 3, big-endian
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t le = (uint32_t)(a[i >> 1] >> (32 * (i & 1)));
+    seed[i] = (le << 24) | ((le & 0xff00u) << 8) | ((le >> 8) & 0xff00u) | (le >> 24);
+  }
 }
 // Each pad byte is the low byte of one next_u32, so ChaCha block j (the 128-bit counter of rand
 // 0.4's ChaChaRng = j) yields pad bytes [16 j, 16 j + 16).
@@ -241,6 +252,48 @@ HASH_HD void enc_pad_block(uint8_t out[16], const uint32_t seed[8], uint64_t blo
   rng.state[13] = (uint32_t)(block >> 32);
   rng.refill();
   for (int i = 0; i < 16; ++i) out[i] = (uint8_t)rng.buf[i];
+}
+
+// One lane of the pad (k_enc_pad): block b of the batch belongs to the item i with blk_off[i] <=
+// b < blk_off[i + 1] (blk_off[n] = the batch's block count); its up to 16 bytes of
+// [offsets[i], offsets[i + 1]) become msg XOR pad, or zero when the item's gate is not 0 (ACCEPT).
+HASH_HD void enc_pad_lane(uint32_t b, uint32_t n, const uint32_t* __restrict__ blk_off,
+                          const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ seeds,
+                          const int32_t* __restrict__ gate, const uint8_t* __restrict__ msgs,
+                          uint8_t* __restrict__ out_v) {
+  uint32_t lo = 0, hi = n;  // blk_off[lo] <= b < blk_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (blk_off[mid] <= b)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const uint32_t i = lo, j = b - blk_off[i];
+  const uint32_t start = offsets[i] + 16u * j, end = offsets[i + 1];
+  const uint32_t cnt = end - start < 16u ? end - start : 16u;
+  uint8_t pad[16];
+  const bool ok = gate[i] == 0;
+  if (ok) {
+    uint32_t seed[8];
+    for (int t = 0; t < 8; ++t) seed[t] = seeds[8 * (size_t)i + t];
+    enc_pad_block(pad, seed, j);
+  }
+#pragma unroll
+  for (uint32_t t = 0; t < 16; ++t)
+    if (t < cnt) out_v[start + t] = ok ? (uint8_t)(msgs[start + t] ^ pad[t]) : (uint8_t)0;
+}
+
+// One item of k_dec_seed: the pad seed of a combined g (its 48 compressed bytes as 12 words; the
+// infinity encoding 0xC0 00.. is hashed like any other, as the reference's hash_bytes does), or
+// zeros for an item whose gate did not pass.  Returns the pad's gate: 0 (ACCEPT) or 1.
+HASH_HD int32_t dec_seed_item(uint32_t seed[8], const uint32_t g_words[12], bool pass) {
+  if (!pass) {
+    for (int t = 0; t < 8; ++t) seed[t] = 0;
+    return 1;
+  }
+  enc_pad_seed(seed, g_words);
+  return 0;
 }
 
 // ---- Fr polynomials

@@ -203,6 +203,14 @@ struct hbtc_ctx {
     hipEvent_t ev;
   };
   std::vector<PendingRead> comb_reads;
+  // Device ranges a pending G1 combine writes (g, the instance statuses), with the lane it runs
+  // on: hbtc_pad_xor_dev orders itself behind them on the device (hbtc.h, Threading).
+  struct PendingWrite {
+    uintptr_t lo, hi;
+    hipEvent_t ev;
+    int lane;
+  };
+  std::vector<PendingWrite> comb_writes;
   // the decoded shares of the last RLC DecryptionShare verification (reused by a combine of
   // the same item arrays: no second decode / subgroup check)
   struct LastDec {
@@ -234,6 +242,8 @@ struct hbtc_ctx {
     int32_t* inst_status = nullptr;
     size_t n_items = 0, n_inst = 0, pt = 0;
     bool combined = false;
+    uint8_t* plain = nullptr;  // hbtc_dec_epoch_submit_plain: the caller's plaintext buffer
+    size_t n_plain = 0;
   };
   Ticket tickets[NL];
   uint64_t next_ticket = 1;
@@ -1222,9 +1232,9 @@ int msm_run(hbtc_ctx* c, hipStream_t st, const MsmPlan& p, const uint32_t* d_sca
 // combined; with d_item_status, the first t items whose status is ACCEPT (hbbft combines only
 // verified shares: coin.rs:185-191 iterates `received_shares`, td.rs:184 `shares`, both holding
 // verified shares only).
-int combine_dev(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets,
+int combine_run(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets,
                 const uint32_t* d_idx, const uint8_t* d_pts, uint32_t t, uint8_t* d_out,
-                uint8_t* d_parity, int32_t* d_inst_status, const int32_t* d_item_status = nullptr) {
+                uint8_t* d_parity, int32_t* d_inst_status, const int32_t* d_item_status) {
   uint32_t n_items;
   HB_TRY(check_offsets(c, n_inst, offsets, &n_items));
   if (n_inst == 0) return HBTC_OK;
@@ -1388,6 +1398,75 @@ int combine_dev(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets
                              {dec2, dec2 ? n_items * sizeof(G2A) : 0}});
 }
 
+// The combine proper, then (G1) a note of what it writes until it completes, for the reads that
+// follow it without a host wait (pad_xor_dev).
+int combine_dev(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets,
+                const uint32_t* d_idx, const uint8_t* d_pts, uint32_t t, uint8_t* d_out,
+                uint8_t* d_parity, int32_t* d_inst_status, const int32_t* d_item_status = nullptr) {
+  HB_TRY(combine_run(c, group, n_inst, offsets, d_idx, d_pts, t, d_out, d_parity, d_inst_status,
+                     d_item_status));
+  if (group != 1 || n_inst == 0) return HBTC_OK;
+  auto& v = c->comb_writes;
+  for (size_t i = 0; i < v.size();) {  // forget combines that have completed
+    if (hipEventQuery(v[i].ev) != hipSuccess) {
+      ++i;
+      continue;
+    }
+    (void)hipEventDestroy(v[i].ev);
+    v[i] = v.back();
+    v.pop_back();
+  }
+  const std::pair<const void*, size_t> wr[2] = {{d_out, (size_t)48 * n_inst}, {d_inst_status, (size_t)4 * n_inst}};
+  for (const auto& r : wr) {
+    hipEvent_t ev;
+    HB_CHECK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HB_CHECK(c, hipEventRecord(ev, c->s_comb));
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(r.first);
+    v.push_back({lo, lo + r.second, ev, c->lane});
+  }
+  return HBTC_OK;
+}
+
+// First pad block of every item (16 pad bytes per ChaCha block; blk[n] = the call's block count).
+int pad_block_table(hbtc_ctx* c, uint32_t n, const uint32_t* offsets, std::vector<uint32_t>& blk) {
+  blk.resize((size_t)n + 1);
+  uint64_t nb = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    blk[i] = (uint32_t)nb;
+    nb += ((uint64_t)(offsets[i + 1] - offsets[i]) + 15) / 16;
+  }
+  if (nb > 0xffffff00ull) return fail(c, HBTC_ERR_ARG, "too many pad blocks in one call");
+  blk[n] = (uint32_t)nb;
+  return HBTC_OK;
+}
+
+// The pad behind a g (a combine's, or a multiplication's): k_dec_seed gated on d_gate / d_gate2
+// (either may be null), then k_enc_pad over the n items' ranges of d_v -> d_out, all on `st`; the
+// offset tables go through pinned stages ordered on the same stream.  *d_item_st (optional): the
+// per-item status k_dec_seed wrote (ACCEPT / d_gate's failure / DECODE_ERR), in the lane's workspace.
+int dec_pad_dev(hbtc_ctx* c, hipStream_t st, uint32_t n, const uint8_t* d_g, const int32_t* d_gate,
+                const int32_t* d_gate2, const uint32_t* v_offsets, const uint8_t* d_v, uint8_t* d_out,
+                const int32_t** d_item_st = nullptr) {
+  if (n == 0) return HBTC_OK;
+  if (!aligned16(d_g)) return fail(c, HBTC_ERR_ARG, "g must be 16-byte aligned");
+  std::vector<uint32_t> blk;
+  HB_TRY(pad_block_table(c, n, v_offsets, blk));
+  void *p_off, *p_blk;
+  HB_TRY(stage_upload(c, "dp.off", v_offsets, ((size_t)n + 1) * 4, st, &p_off));
+  HB_TRY(stage_upload(c, "dp.blk", blk.data(), ((size_t)n + 1) * 4, st, &p_blk));
+  uint32_t* d_seed;
+  int32_t* d_pst;
+  HB_TRY(wst(c, "dp.seed", (size_t)8 * n, &d_seed));
+  HB_TRY(wst(c, "dp.gate", n, &d_pst));
+  if (d_item_st) *d_item_st = d_pst;
+  return timed_on(c, st, "dec_pad", [&] {
+    const hipError_t e = launch_dec_seed(st, n, d_g, d_gate, d_gate2, d_seed, d_pst);
+    if (e != hipSuccess) return e;
+    return launch_enc_pad(st, n, blk[n], (const uint32_t*)p_blk, (const uint32_t*)p_off, d_seed, d_pst,
+                          d_v, d_out);
+  });
+}
+
 int point_mul_host(hbtc_ctx* c, int group, uint32_t n, const uint8_t* base,
                    uint32_t base_stride, const uint8_t* scalars, uint8_t* out, int32_t* status) {
   const size_t pb = group == 1 ? 48 : 96;
@@ -1434,11 +1513,13 @@ int finish_ticket(hbtc_ctx* c, hbtc_ctx::Ticket& T) {
   memcpy(T.status, o, 4 * T.n_items);
   off = round256(4 * T.n_items);
   if (T.combined) {
-    memcpy(T.out, o + off, T.pt * T.n_inst);
+    if (T.out) memcpy(T.out, o + off, T.pt * T.n_inst);
     off += round256(T.pt * T.n_inst);
     if (T.parity) memcpy(T.parity, o + off, T.n_inst);
     off += round256(T.n_inst);
     memcpy(T.inst_status, o + off, 4 * T.n_inst);
+    off += round256(4 * T.n_inst);
+    if (T.plain && T.n_plain) memcpy(T.plain, o + off, T.n_plain);
   }
   T.active = false;
   return HBTC_OK;
@@ -1447,10 +1528,13 @@ int finish_ticket(hbtc_ctx* c, hbtc_ctx::Ticket& T) {
 // One epoch from host buffers without blocking: inputs into the next lane's pinned staging,
 // H2D, verification, the combine of the first t verified shares of every instance (t > 0) and
 // D2H of the results, all on that lane's stream (group 1: DecryptionShares, 2: SignatureShares).
+// With v_off (group 1, t > 0): the ciphertexts' v ride in the same staging, the seed and the pad
+// follow the combine on the lane's stream and the plaintexts come back with the other results.
 int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H,
                  const uint8_t* w, const uint32_t* offsets, const uint32_t* idx, const uint8_t* items,
                  uint32_t t, int32_t* status, uint8_t* out, uint8_t* parity, int32_t* inst_status,
-                 uint64_t* ticket) {
+                 uint64_t* ticket, const uint8_t* v = nullptr, const uint32_t* v_off = nullptr,
+                 uint8_t* out_plain = nullptr) {
   uint32_t n;
   HB_TRY(check_offsets(c, n_inst, offsets, &n));
   const size_t pt = group == 1 ? 48 : 96;
@@ -1460,14 +1544,17 @@ int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, co
   if (!T.ev) HB_CHECK(c, hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
   select_lane(c, l);
   const size_t sH = 96 * (size_t)n_inst, sW = group == 1 ? sH : 0, sI = 4 * (size_t)n, sP = pt * n;
-  const size_t oW = round256(sH), oI = oW + round256(sW), oP = oI + round256(sI);
-  HB_TRY(pinned_grow(c, &T.h_in, &T.in_cap, oP + sP));
+  const size_t sV = v_off ? v_off[n_inst] : 0;
+  const size_t oW = round256(sH), oI = oW + round256(sW), oP = oI + round256(sI), oV = oP + round256(sP);
+  HB_TRY(pinned_grow(c, &T.h_in, &T.in_cap, oV + sV));
   uint8_t* hi = static_cast<uint8_t*>(T.h_in);
   if (sH) memcpy(hi, H, sH);
   if (sW) memcpy(hi + oW, w, sW);
   if (sI) memcpy(hi + oI, idx, sI);
   if (sP) memcpy(hi + oP, items, sP);
+  if (sV) memcpy(hi + oV, v, sV);
   void *d_H, *d_w = nullptr, *d_idx, *d_items, *d_st, *d_out = nullptr, *d_par = nullptr, *d_cst = nullptr;
+  void *d_v = nullptr, *d_plain = nullptr;
   HB_TRY(ws(c, "ep.H", sH, &d_H));
   if (sW) HB_TRY(ws(c, "ep.w", sW, &d_w));
   HB_TRY(ws(c, "ep.idx", sI, &d_idx));
@@ -1480,6 +1567,11 @@ int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, co
   if (sW) HB_CHECK(c, hipMemcpyAsync(d_w, hi + oW, sW, hipMemcpyHostToDevice, c->stream));
   if (sI) HB_CHECK(c, hipMemcpyAsync(d_idx, hi + oI, sI, hipMemcpyHostToDevice, c->stream));
   if (sP) HB_CHECK(c, hipMemcpyAsync(d_items, hi + oP, sP, hipMemcpyHostToDevice, c->stream));
+  if (sV) {
+    HB_TRY(ws(c, "ep.v", sV, &d_v));
+    HB_TRY(ws(c, "ep.plain", sV, &d_plain));
+    HB_CHECK(c, hipMemcpyAsync(d_v, hi + oV, sV, hipMemcpyHostToDevice, c->stream));
+  }
   const bool comb = t > 0 && n_inst > 0;
   {
     PinLane pin(c);  // the uploads above went to lane l: verification and combine stay there
@@ -1496,17 +1588,22 @@ int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, co
       HB_TRY(ws(c, "ep.cst", 4 * (size_t)n_inst, &d_cst));
       HB_TRY(combine_dev(c, group, n_inst, offsets, (const uint32_t*)d_idx, (const uint8_t*)d_items, t,
                          (uint8_t*)d_out, (uint8_t*)d_par, (int32_t*)d_cst, (const int32_t*)d_st));
+      if (sV)
+        HB_TRY(dec_pad_dev(c, c->s_comb, n_inst, (const uint8_t*)d_out, (const int32_t*)d_cst, nullptr,
+                           v_off, (const uint8_t*)d_v, (uint8_t*)d_plain));
       HB_TRY(stream_after(c, c->stream, c->s_comb, c->ev_comb));
     }
   }
   const size_t q1 = round256(4 * (size_t)n), q2 = q1 + round256(pt * n_inst), q3 = q2 + round256(n_inst);
-  HB_TRY(pinned_grow(c, &T.h_out, &T.out_cap, q3 + 4 * (size_t)n_inst + 16));
+  const size_t q4 = q3 + round256(4 * (size_t)n_inst);
+  HB_TRY(pinned_grow(c, &T.h_out, &T.out_cap, q4 + sV + 16));
   uint8_t* ho = static_cast<uint8_t*>(T.h_out);
   if (n) HB_CHECK(c, hipMemcpyAsync(ho, d_st, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (comb) {
     HB_CHECK(c, hipMemcpyAsync(ho + q1, d_out, pt * n_inst, hipMemcpyDeviceToHost, c->stream));
     if (d_par) HB_CHECK(c, hipMemcpyAsync(ho + q2, d_par, n_inst, hipMemcpyDeviceToHost, c->stream));
     HB_CHECK(c, hipMemcpyAsync(ho + q3, d_cst, 4 * (size_t)n_inst, hipMemcpyDeviceToHost, c->stream));
+    if (sV) HB_CHECK(c, hipMemcpyAsync(ho + q4, d_plain, sV, hipMemcpyDeviceToHost, c->stream));
   }
   HB_CHECK(c, hipEventRecord(T.ev, c->stream));
   T.status = status;
@@ -1517,6 +1614,8 @@ int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, co
   T.n_inst = n_inst;
   T.pt = pt;
   T.combined = comb;
+  T.plain = comb && sV ? out_plain : nullptr;
+  T.n_plain = sV;
   T.active = true;
   T.id = c->next_ticket++;
   *ticket = T.id;
@@ -1650,6 +1749,7 @@ void hbtc_ctx_destroy(hbtc_ctx* c) {
     (void)hipEventDestroy(sp.b);
   }
   for (auto& r : c->comb_reads) (void)hipEventDestroy(r.ev);
+  for (auto& r : c->comb_writes) (void)hipEventDestroy(r.ev);
   for (auto& kv : c->gf_plans) {
     (void)hipFree(kv.second.out_rows);
     (void)hipFree(kv.second.in_rows);
@@ -2313,6 +2413,47 @@ int hbtc_combine_dec(hbtc_ctx* c, uint32_t n_ct, const uint32_t* offsets, const 
   return sync(c);
 }
 
+int hbtc_threshold_decrypt(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_ct, const uint8_t* H,
+                           const uint8_t* w, const uint32_t* offsets, const uint32_t* idx,
+                           const uint8_t* share, uint32_t t, const uint8_t* v, const uint32_t* v_offsets,
+                           int32_t* status, uint8_t* out_g, uint8_t* out_plain, int32_t* inst_status) {
+  if (!c || (n_ct && (!H || !w || !offsets || !v_offsets || !inst_status))) return HBTC_ERR_ARG;
+  Guard g(c);
+  if (n_ct == 0) return HBTC_OK;
+  uint32_t n;
+  HB_TRY(check_offsets(c, n_ct, offsets, &n));
+  if (n && (!idx || !share || !status)) return fail(c, HBTC_ERR_ARG, "NULL item array");
+  if (t == 0) return fail(c, HBTC_ERR_ARG, "t must be >= 1");
+  if (!hash_offsets_ok(n_ct, v_offsets)) return fail(c, HBTC_ERR_ARG, "v_offsets must start at 0 and not decrease");
+  const size_t total = v_offsets[n_ct];
+  if (total && (!v || !out_plain)) return fail(c, HBTC_ERR_ARG, "NULL plaintext array");
+  void *d_H, *d_w, *d_idx, *d_sh, *d_v, *d_st, *d_g, *d_cst, *d_plain;
+  HB_TRY(upload(c, "in0", H, (size_t)96 * n_ct, &d_H));
+  HB_TRY(upload(c, "in1", w, (size_t)96 * n_ct, &d_w));
+  HB_TRY(upload(c, "in2", idx, (size_t)4 * n, &d_idx));
+  HB_TRY(upload(c, "in3", share, (size_t)48 * n, &d_sh));
+  HB_TRY(upload(c, "in4", v, total, &d_v));
+  HB_TRY(ws(c, "out0", (size_t)4 * n, &d_st));
+  HB_TRY(ws(c, "out1", (size_t)48 * n_ct, &d_g));
+  HB_TRY(ws(c, "out2", (size_t)4 * n_ct, &d_cst));
+  HB_TRY(ws(c, "out3", total, &d_plain));
+  PinLane pin(c);  // the uploads above went to the current lane
+  HostG2Args hg(c, d_H, H, d_w, w);
+  HB_TRY(dec_shares_dev(c, keyset_id, n_ct, (const uint8_t*)d_H, (const uint8_t*)d_w, offsets,
+                        (const uint32_t*)d_idx, (const uint8_t*)d_sh, (int32_t*)d_st));
+  // combine, seed and pad follow the verification on the lane's stream: no host wait in between
+  HB_TRY(combine_dev(c, 1, n_ct, offsets, (const uint32_t*)d_idx, (const uint8_t*)d_sh, t, (uint8_t*)d_g,
+                     nullptr, (int32_t*)d_cst, (const int32_t*)d_st));
+  HB_TRY(dec_pad_dev(c, c->s_comb, n_ct, (const uint8_t*)d_g, (const int32_t*)d_cst, nullptr, v_offsets,
+                     (const uint8_t*)d_v, (uint8_t*)d_plain));
+  HB_TRY(stream_after(c, c->stream, c->s_comb, c->ev_comb));
+  HB_TRY(download(c, status, d_st, (size_t)4 * n));
+  if (out_g) HB_TRY(download(c, out_g, d_g, (size_t)48 * n_ct));
+  HB_TRY(download(c, inst_status, d_cst, (size_t)4 * n_ct));
+  HB_TRY(download(c, out_plain, d_plain, total));
+  return sync(c);
+}
+
 int hbtc_g1_mul(hbtc_ctx* c, uint32_t n, const uint8_t* base, uint32_t base_stride,
                 const uint8_t* scalars, uint8_t* out, int32_t* status) {
   if (!c || (n && (!base || !scalars || !out || !status))) return HBTC_ERR_ARG;
@@ -2416,6 +2557,28 @@ int hbtc_dec_epoch_submit(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_ct, const 
                       nullptr, inst_status, ticket);
 }
 
+int hbtc_dec_epoch_submit_plain(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_ct, const uint8_t* H_c96,
+                                const uint8_t* w_c96, const uint32_t* offsets, const uint32_t* idx,
+                                const uint8_t* share_c48, uint32_t t, const uint8_t* v,
+                                const uint32_t* v_offsets, int32_t* status, uint8_t* out_g_c48,
+                                uint8_t* out_plain, int32_t* inst_status, uint64_t* ticket) {
+  if (!c || !ticket || (n_ct && (!H_c96 || !w_c96 || !offsets || !v_offsets))) return HBTC_ERR_ARG;
+  Guard g(c);
+  uint32_t n;
+  HB_TRY(check_offsets(c, n_ct, offsets, &n));
+  if (n && (!idx || !share_c48 || !status)) return fail(c, HBTC_ERR_ARG, "NULL item array");
+  if (t == 0) return fail(c, HBTC_ERR_ARG, "t must be >= 1");
+  if (n_ct && !inst_status) return fail(c, HBTC_ERR_ARG, "NULL combine output");
+  static const uint32_t no_v[1] = {0};
+  if (n_ct == 0) v_offsets = no_v;
+  if (!hash_offsets_ok(n_ct, v_offsets)) return fail(c, HBTC_ERR_ARG, "v_offsets must start at 0 and not decrease");
+  if (v_offsets[n_ct] && (!v || !out_plain)) return fail(c, HBTC_ERR_ARG, "NULL plaintext array");
+  std::vector<uint32_t> blk;
+  HB_TRY(pad_block_table(c, n_ct, v_offsets, blk));  // refuse before anything is enqueued
+  return epoch_submit(c, 1, keyset_id, n_ct, H_c96, w_c96, offsets, idx, share_c48, t, status, out_g_c48,
+                      nullptr, inst_status, ticket, v, v_offsets, out_plain);
+}
+
 int hbtc_sig_epoch_submit(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H_c96,
                           const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_c96,
                           uint32_t t, int32_t* status, uint8_t* out_sig_c96, uint8_t* out_parity,
@@ -2480,6 +2643,39 @@ int hbtc_combine_dec_verified_dev(hbtc_ctx* c, uint32_t n_ct, const uint32_t* of
   Guard g(c);
   return combine_dev(c, 1, n_ct, offsets, d_idx, d_share, t, d_out_g, nullptr, d_inst_status,
                      d_status);
+}
+
+int hbtc_pad_xor_dev(hbtc_ctx* c, uint32_t n, const uint8_t* d_g, const int32_t* d_gate,
+                     const uint32_t* v_offsets, const uint8_t* d_v, uint8_t* d_out) {
+  if (!c) return HBTC_ERR_ARG;
+  Guard g(c);
+  if (n == 0) return HBTC_OK;
+  if (!d_g || !v_offsets || !hash_offsets_ok(n, v_offsets)) return fail(c, HBTC_ERR_ARG, "pad_xor: bad arguments");
+  const size_t total = v_offsets[n];
+  if (total && (!d_v || !d_out)) return fail(c, HBTC_ERR_ARG, "NULL plaintext array");
+  // run on the lane of the latest pending combine that writes g or the gate (behind it, in stream
+  // order), and wait on the device for any other such combine
+  const std::vector<std::pair<uintptr_t, uintptr_t>> rd = {rng(d_g, (size_t)48 * n),
+                                                          rng(d_gate, d_gate ? (size_t)4 * n : 0)};
+  int on = -1;
+  std::vector<hipEvent_t> others;
+  for (auto it = c->comb_writes.rbegin(); it != c->comb_writes.rend(); ++it) {
+    if (!ranges_overlap(rd, {{it->lo, it->hi}})) continue;
+    if (on < 0) on = it->lane;
+    if (it->lane != on) others.push_back(it->ev);
+  }
+  const int cur = c->lane;
+  if (on >= 0) select_lane(c, on);
+  int rc = HBTC_OK;
+  for (hipEvent_t ev : others)
+    if (rc == HBTC_OK && hipStreamWaitEvent(c->s_comb, ev, 0) != hipSuccess)
+      rc = fail(c, HBTC_ERR_DEVICE, "pad_xor: hipStreamWaitEvent");
+  if (rc == HBTC_OK) rc = guard_write(c, d_out, total);  // a combine still reading the output range
+  if (rc == HBTC_OK) rc = dec_pad_dev(c, c->s_comb, n, d_g, d_gate, nullptr, v_offsets, d_v, d_out);
+  if (rc == HBTC_OK)  // later uploads into what the pad reads wait for it (guard_write)
+    rc = note_comb_reads(c, {{d_g, (size_t)48 * n}, {d_gate, d_gate ? (size_t)4 * n : 0}, {d_v, total}});
+  select_lane(c, cur);
+  return rc;
 }
 
 int hbtc_combine_sigs_verified_dev(hbtc_ctx* c, uint32_t n_inst, const uint32_t* offsets,
@@ -3012,8 +3208,14 @@ int hbtc_timing_reset(hbtc_ctx* c) {
 // hash_g2(msg_i) (g1 == null) or hash_g1_g2(g1_i, msg_i) for a batch, entirely on the GPU: the
 // candidate draw (k_hash_cand: sha3, rand 0.4 ChaCha, G2::rand's loop) and [h2] P; a candidate
 // whose [h2] P is O (probability ~2^-250) continues G2::rand's loop on the host (exact).
+// out_c96 == nullptr: the hashes are not downloaded.  keep: the call's device buffers (the current
+// lane's workspace, valid until its next hash batch), the redrawn items patched in d_out.
+struct HashKeep {
+  uint8_t* d_out = nullptr;         // n compressed G2 hashes
+  const uint8_t* d_msgs = nullptr;  // the messages as uploaded
+};
 static int hash_batch_gpu(hbtc_ctx* c, uint32_t n, const uint8_t* g1_c48, const uint8_t* msgs,
-                          const uint32_t* offsets, uint8_t* out_c96, uint8_t** d_out_keep = nullptr) {
+                          const uint32_t* offsets, uint8_t* out_c96, HashKeep* keep = nullptr) {
   HB_TRY(sync(c));
   void *d_msgs, *d_off, *d_g1 = nullptr;
   G2A* d_cand;
@@ -3031,18 +3233,25 @@ static int hash_batch_gpu(hbtc_ctx* c, uint32_t n, const uint8_t* g1_c48, const 
   }));
   HB_TRY(timed(c, "hash", [&] { return launch_g2_clear_cofactor(c->stream, n, d_cand, d_out, d_st); }));
   std::vector<int32_t> st(n);
-  HB_CHECK(c, hipMemcpyAsync(out_c96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, c->stream));
+  if (out_c96)
+    HB_CHECK(c, hipMemcpyAsync(out_c96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, c->stream));
   HB_CHECK(c, hipMemcpyAsync(st.data(), d_st, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   HB_TRY(sync(c));
   for (uint32_t i = 0; i < n; ++i)  // [h2] P = O: G2::rand draws again (host, exact)
     if (st[i]) {
+      uint8_t h[96];
       if (g1_c48)
-        hash_g1_g2_c96(g1_c48 + 48 * (size_t)i, msgs + offsets[i], offsets[i + 1] - offsets[i],
-                       out_c96 + 96 * (size_t)i);
+        hash_g1_g2_c96(g1_c48 + 48 * (size_t)i, msgs + offsets[i], offsets[i + 1] - offsets[i], h);
       else
-        hash_g2_c96(msgs + offsets[i], offsets[i + 1] - offsets[i], out_c96 + 96 * (size_t)i);
+        hash_g2_c96(msgs + offsets[i], offsets[i + 1] - offsets[i], h);
+      if (out_c96) memcpy(out_c96 + 96 * (size_t)i, h, 96);
+      if (keep)  // only the redrawn items go back up
+        HB_CHECK(c, hipMemcpy(d_out + 96 * (size_t)i, h, 96, hipMemcpyHostToDevice));
     }
-  if (d_out_keep) *d_out_keep = d_out;
+  if (keep) {
+    keep->d_out = d_out;
+    keep->d_msgs = static_cast<const uint8_t*>(d_msgs);
+  }
   return HBTC_OK;
 }
 
@@ -3120,20 +3329,23 @@ int hbtc_decrypt(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t*
       !hash_offsets_ok(n, offsets))
     return HBTC_ERR_ARG;
   Guard g(c);
-  // 1. H_i = hash_g1_g2(u_i, v_i) on the GPU
-  std::vector<uint8_t> H((size_t)n * 96);
-  HB_TRY(hash_batch_gpu(c, n, u_c48, msgs, offsets, H.data()));
+  std::vector<uint32_t> blk;
+  HB_TRY(pad_block_table(c, n, offsets, blk));  // refuse before anything is enqueued
+  // 1. H_i = hash_g1_g2(u_i, v_i) on the GPU; H and the uploaded v stay there
+  HashKeep hk;
+  HB_TRY(hash_batch_gpu(c, n, u_c48, msgs, offsets, nullptr, &hk));
   // 2. Ciphertext::verify: e(G1, w) == e(u, H);  3. g = sk * u
   Fr k;
   scalar_mod_r(k.v, sk_le32);
-  void *d_u, *d_H, *d_w, *d_st, *d_k, *d_g, *d_gst;
+  void *d_u, *d_H = hk.d_out, *d_w, *d_st, *d_k, *d_g, *d_gst, *d_plain;
+  const size_t total = offsets[n];
   HB_TRY(upload(c, "in0", u_c48, (size_t)48 * n, &d_u));
-  HB_TRY(upload(c, "in1", H.data(), (size_t)96 * n, &d_H));
   HB_TRY(upload(c, "in2", w_c96, (size_t)96 * n, &d_w));
   HB_TRY(upload(c, "in3", k.v, 32, &d_k));
   HB_TRY(ws(c, "out0", (size_t)4 * n, &d_st));
   HB_TRY(ws(c, "out1", (size_t)48 * n, &d_g));
   HB_TRY(ws(c, "out2", (size_t)4 * n, &d_gst));
+  HB_TRY(ws(c, "out3", total, &d_plain));
   // H is this call's own hash output (cofactor cleared: in the subgroup by construction)
   const bool rlc = c->verify_mode == HBTC_MODE_RLC;
   G1A* d_adec = nullptr;
@@ -3148,32 +3360,21 @@ int hbtc_decrypt(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t*
     HB_TRY(timed(c, "mul", [&] {
       return launch_pb_mul_glv(c->stream, n, d_adec, (const int32_t*)d_st, k0, k1, (uint8_t*)d_g);
     }));
-    HB_CHECK(c, hipMemsetAsync(d_gst, 0, (size_t)4 * n, c->stream));  // statuses are in d_st
+    d_gst = nullptr;  // statuses are in d_st
   } else {
     HB_TRY(timed(c, "mul", [&] {
       return launch_point_mul(c->stream, 1, n, (const uint8_t*)d_u, 1, (const uint8_t*)d_k, 0,
                               (uint8_t*)d_g, (int32_t*)d_gst);
     }));
   }
-  std::vector<uint8_t> gb((size_t)n * 48);
-  std::vector<int32_t> gst(n);
-  HB_TRY(download(c, status, d_st, (size_t)4 * n));
-  HB_TRY(download(c, gb.data(), d_g, (size_t)48 * n));
-  HB_TRY(download(c, gst.data(), d_gst, (size_t)4 * n));
-  HB_TRY(sync(c));
-  // 4. plaintext = v XOR hash_bytes(g, |v|) for the ciphertexts that verify
-  parallel_items(n, [&](uint32_t i) {
-    if (status[i] == HBTC_ACCEPT && gst[i] != HBTC_ACCEPT) status[i] = HBTC_DECODE_ERR;
-    const size_t len = offsets[i + 1] - offsets[i];
-    uint8_t* o = out + offsets[i];
-    if (status[i] != HBTC_ACCEPT) {
-      if (len) memset(o, 0, len);
-      return;
-    }
-    hash_bytes(gb.data() + 48 * (size_t)i, len, o);
-    for (size_t j2 = 0; j2 < len; ++j2) o[j2] ^= msgs[offsets[i] + j2];
-  });
-  return HBTC_OK;
+  // 4. plaintext = v XOR hash_bytes(g, |v|) for the ciphertexts that verify (zeros for the
+  // others), behind the multiplication: ACCEPT in d_st with a failed multiplication is DECODE_ERR
+  const int32_t* d_fst;
+  HB_TRY(dec_pad_dev(c, c->stream, n, (const uint8_t*)d_g, (const int32_t*)d_st, (const int32_t*)d_gst,
+                     offsets, hk.d_msgs, (uint8_t*)d_plain, &d_fst));
+  HB_TRY(download(c, status, d_fst, (size_t)4 * n));
+  HB_TRY(download(c, out, d_plain, total));
+  return sync(c);
 }
 
 int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_stride,
@@ -3185,15 +3386,9 @@ int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_str
       (offsets[n] && (!msgs || !out_v)) || !hash_offsets_ok(n, offsets))
     return HBTC_ERR_ARG;
   Guard g(c);
-  // first block of every item's pad (16 pad bytes per ChaCha block)
-  std::vector<uint32_t> blk(n + 1);
-  uint64_t nb = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    blk[i] = (uint32_t)nb;
-    nb += ((uint64_t)(offsets[i + 1] - offsets[i]) + 15) / 16;
-  }
-  if (nb > 0xffffff00ull) return fail(c, HBTC_ERR_ARG, "encrypt: too many pad blocks in one call");
-  blk[n] = (uint32_t)nb;
+  std::vector<uint32_t> blk;
+  HB_TRY(pad_block_table(c, n, offsets, blk));
+  const uint32_t nb = blk[n];
   const size_t total = offsets[n];
   if (!c->enc_tab) {  // the generator's window table, once per context
     EncPt* tab = nullptr;

@@ -5,6 +5,8 @@
 //   pk bytes --k_g1_decode--> pk (affine, subgroup-checked)          [hbtc_kernels.hip]
 //   r, pk ----k_enc_g1------> u = r G1 (comb table), seed = sha3_256(compressed r pk) (GLV)
 //   seed, msg -k_enc_pad----> v = msg XOR hash_bytes(r pk), one lane per 16-byte ChaCha block
+//   g --------k_dec_seed----> seed = sha3_256(compressed g) of a combined / multiplied g: the
+//                             consuming half (decryption), which then runs the same k_enc_pad
 //   u, v -----k_hash_cand---> the first on-curve candidate of hash_g1_g2(u, v)   [hbtc_hash.hip]
 //   cand, r --k_enc_w-------> w = [r] [h2] cand on lane pairs, compressed
 //
@@ -100,27 +102,30 @@ __global__ void __launch_bounds__(256) k_enc_pad(uint32_t n, uint32_t n_blocks,
                                                  uint8_t* __restrict__ out_v) {
   const uint32_t b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n_blocks) return;
-  uint32_t lo = 0, hi = n;  // blk_off[lo] <= b < blk_off[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (blk_off[mid] <= b)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  const uint32_t i = lo, j = b - blk_off[i];
-  const uint32_t start = offsets[i] + 16u * j, end = offsets[i + 1];
-  const uint32_t cnt = end - start < 16u ? end - start : 16u;
-  uint8_t pad[16];
-  const bool ok = status[i] == HBTC_ACCEPT;
-  if (ok) {
-    uint32_t seed[8];
-    for (int t = 0; t < 8; ++t) seed[t] = seeds[8 * (size_t)i + t];
-    enc_pad_block(pad, seed, j);
-  }
-#pragma unroll
-  for (uint32_t t = 0; t < 16; ++t)
-    if (t < cnt) out_v[start + t] = ok ? (uint8_t)(msgs[start + t] ^ pad[t]) : (uint8_t)0;
+  enc_pad_lane(b, n, blk_off, offsets, seeds, status, msgs, out_v);
+}
+
+// The consuming half (PublicKeySet::decrypt / SecretKey::decrypt after g is known): one lane per
+// ciphertext turns the compressed g into the seed of its pad, seeds[i] = sha3_256(g_i), gated on
+// the statuses that produced g (a combine's inst_status, or a verification's and a
+// multiplication's; either may be null = passes).  gate_out[i] is the status of the item: ACCEPT,
+// the first gate's failure, or DECODE_ERR where only the second failed; k_enc_pad reads it as its
+// gate and zero-fills the others' ranges.
+__global__ void __launch_bounds__(64) k_dec_seed(uint32_t n, const uint8_t* __restrict__ g_c48,
+                                                 const int32_t* __restrict__ gate,
+                                                 const int32_t* __restrict__ gate2,
+                                                 uint32_t* __restrict__ seeds,
+                                                 int32_t* __restrict__ gate_out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t s1 = gate ? gate[i] : HBTC_ACCEPT, s2 = gate2 ? gate2[i] : HBTC_ACCEPT;
+  const bool pass = s1 == HBTC_ACCEPT && s2 == HBTC_ACCEPT;
+  uint32_t w[12], seed[8];
+  for (int j = 0; j < 12; ++j) w[j] = 0;
+  if (pass) enc_load_words(w, g_c48, i, 12);
+  const int32_t closed = dec_seed_item(seed, w, pass);
+  enc_store_words(seeds, i, seed, 8);
+  gate_out[i] = closed == 0 ? HBTC_ACCEPT : (s1 != HBTC_ACCEPT ? s1 : HBTC_DECODE_ERR);
 }
 
 // w = [r] hash_g1_g2(u, v) from the hash candidate, on lane pairs (pair.h; item i on lanes 2i,
@@ -248,6 +253,14 @@ hipError_t launch_enc_pad(hipStream_t s, uint32_t n, uint32_t n_blocks, const ui
   if (n == 0 || n_blocks == 0) return hipSuccess;
   hipLaunchKernelGGL(k_enc_pad, dim3(enc_blocks(n_blocks, 256)), dim3(256), 0, s, n, n_blocks, blk_off,
                      offsets, seeds, status, msgs, out_v);
+  return hipGetLastError();
+}
+
+hipError_t launch_dec_seed(hipStream_t s, uint32_t n, const uint8_t* g_c48, const int32_t* gate,
+                           const int32_t* gate2, uint32_t* seeds, int32_t* gate_out) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dec_seed, dim3(enc_blocks(n, 64)), dim3(64), 0, s, n, g_c48, gate, gate2, seeds,
+                     gate_out);
   return hipGetLastError();
 }
 

@@ -364,6 +364,11 @@ hipError_t launch_enc_g1(hipStream_t s, uint32_t n, const G1A* pk, const int32_t
 hipError_t launch_enc_pad(hipStream_t s, uint32_t n, uint32_t n_blocks, const uint32_t* blk_off,
                           const uint32_t* offsets, const uint32_t* seeds, const int32_t* status,
                           const uint8_t* msgs, uint8_t* out_v);
+// decryption: seeds[i] = sha3_256(g_i) where gate[i] and gate2[i] (either may be null) are ACCEPT,
+// else zeros; gate_out[i] = ACCEPT / gate[i] / DECODE_ERR (only gate2 failed) is launch_enc_pad's
+// status argument.  g_c48 16-byte aligned.
+hipError_t launch_dec_seed(hipStream_t s, uint32_t n, const uint8_t* g_c48, const int32_t* gate,
+                           const int32_t* gate2, uint32_t* seeds, int32_t* gate_out);
 // w = [r] [h2] cand (compressed) on lane pairs; flag[i] = 1: [h2] cand = O, the host finishes it
 hipError_t launch_enc_w(hipStream_t s, uint32_t n, const G2A* cand, const uint8_t* r_le32,
                         const int32_t* status, uint8_t* out_w, uint32_t* flag);

@@ -14,7 +14,9 @@ synchronous mode so the reference's retry-on-error behaviour is kept.
 Inputs are hbbft's wire encodings (compressed points).  H = hash_g2(nonce) / hash_g1_g2(u, v)
 is supplied by the caller (threshold_crypto on the Rust side, per the design), and so is this
 node's own share (signing is producer-side).  ThresholdDecryption outputs the combined point
-g = sum l_i d_i (compressed); plaintext = v XOR hash_bytes(g, |v|) stays with the caller.
+g = sum l_i d_i (compressed) by default; DecryptionEpoch(plaintext=True) outputs what the
+reference's try_output does, the plaintext v XOR hash_bytes(g, |v|), made on the GPU behind the
+combine (hbtc_threshold_decrypt).
 """
 from . import _native as N
 
@@ -207,12 +209,19 @@ class _TdState:
 
 
 class DecryptionEpoch:
-    """Every ThresholdDecryption instance (threshold_decryption.rs:45) of one epoch."""
+    """Every ThresholdDecryption instance (threshold_decryption.rs:45) of one epoch.
 
-    def __init__(self, ctx, netinfo):
+    plaintext=False: a terminated instance outputs the combined point g (48 bytes).
+    plaintext=True: it outputs the plaintext bytes, as try_output does (td.rs:187): the flush's
+    pending combines go through ONE ctx.threshold_decrypt call (shares -> g -> plaintext on the
+    device) with the v, w and H of each instance's stored ciphertext.  That call verifies the
+    shares it combines once more, this node's own share included."""
+
+    def __init__(self, ctx, netinfo, plaintext=False):
         self.ctx = ctx
         self.ni = netinfo
         self.inst = {}
+        self.plaintext = plaintext
 
     def add(self, key, our_share_c48=None):
         self.inst[key] = _TdState(our_share_c48)
@@ -281,9 +290,15 @@ class DecryptionEpoch:
             results[k] = self._replay(k, verdict, ct_ok, pending)
         if pending:
             t = ni.num_faulty + 1
-            g, cst = self.ctx.combine_dec([len(p[2]) for p in pending],
-                                          [i for p in pending for i, _ in p[2]],
-                                          [s for p in pending for _, s in p[2]], t)
+            counts = [len(p[2]) for p in pending]
+            idx = [i for p in pending for i, _ in p[2]]
+            shares = [s for p in pending for _, s in p[2]]
+            if self.plaintext:
+                cts = [self.inst[p[0]].ct for p in pending]  # (u, v, w, H) of a terminated instance
+                _, g, _, cst = self.ctx.threshold_decrypt(ni.keyset, [c[3] for c in cts], [c[2] for c in cts],
+                                                          counts, idx, shares, t, [c[1] for c in cts])
+            else:
+                g, cst = self.ctx.combine_dec(counts, idx, shares, t)
             for (k, step, items), gk, c in zip(pending, g, cst):
                 if int(c) == N.ACCEPT:
                     step["output"] = gk

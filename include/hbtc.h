@@ -11,7 +11,9 @@
  *                                                                             src/coin.rs:185-191,173
  *   hbtc_verify_dec_shares   PublicKeyShare::verify_decryption_share          src/threshold_decryption.rs:159
  *   hbtc_combine_dec         PublicKeySet::decrypt, the G1 interpolation      src/threshold_decryption.rs:181-185
- *                            (plaintext = v XOR hash_bytes(g, |v|) stays with the caller)
+ *                            (g only; the plaintext v XOR hash_bytes(g, |v|) is hbtc_threshold_decrypt's)
+ *   hbtc_threshold_decrypt   ThresholdDecryption::try_output: shares verified, combined and the
+ *                            plaintext v XOR hash_bytes(g, |v|) made on the GPU  src/threshold_decryption.rs:164-188
  *   hbtc_verify_ciphertexts  Ciphertext::verify inside SecretKeyShare::decrypt_share
  *                                                                             src/threshold_decryption.rs:98
  *   hbtc_keyset_load         the public_key_share(idx) table of NetworkInfo::new
@@ -45,7 +47,9 @@
  * device pointers (from hbtc_dev_alloc) and are ordered as issued: combines run on a side
  * stream, concurrently with the verification issued after them, and any later call that
  * writes a device range a pending combine still reads (a status array, an upload into the
- * share buffer) first waits for that combine.
+ * share buffer) first waits for that combine.  The reverse case, a call that READS what a pending
+ * combine writes (hbtc_pad_xor_dev reading d_g_c48 / d_gate_status), is ordered after that combine
+ * on the device, without a host wait.
  * The caller owns every buffer; nothing is retained after a call returns.
  */
 #ifndef HBTC_H
@@ -167,11 +171,29 @@ int hbtc_combine_dec(hbtc_ctx* ctx, uint32_t n_ct, const uint32_t* offsets, cons
                      const uint8_t* share_c48, uint32_t t, uint8_t* out_g_c48,
                      int32_t* inst_status);
 
+/* One ThresholdDecryption round in one blocking call (try_output, src/threshold_decryption.rs:
+ * 164-188): every share verified exactly as hbtc_verify_dec_shares (status[i]), the first t
+ * ACCEPTed shares of each ciphertext combined exactly as hbtc_combine_dec_verified_dev
+ * (inst_status[k], out_g_c48[48 k ..]; out_g_c48 may be NULL), and
+ * out_plain[v_offsets[k] .. v_offsets[k+1]) = v_k XOR hash_bytes(g_k, |v_k|) with v_k =
+ * v[v_offsets[k] .. v_offsets[k+1]) (v_offsets[0] == 0, non-decreasing; the pad-block limit of
+ * hbtc_encrypt).  A ciphertext whose inst_status is not ACCEPT gets a zero-filled plaintext range
+ * and a zero-filled g.  Inputs are uploaded once and outputs downloaded once; verification,
+ * combine, seed (k_dec_seed) and pad (k_enc_pad) follow each other on the device with no host wait
+ * in between (DESIGN.md "Decryption to plaintext").  t >= 1.
+ * Ciphertext validity (Ciphertext::verify at set_ciphertext, src/threshold_decryption.rs:98) is
+ * NOT part of this call: it stays the separate earlier hbtc_verify_ciphertexts call, as before. */
+int hbtc_threshold_decrypt(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_ct, const uint8_t* H_c96,
+                           const uint8_t* w_c96, const uint32_t* offsets, const uint32_t* idx,
+                           const uint8_t* share_c48, uint32_t t, const uint8_t* v,
+                           const uint32_t* v_offsets, int32_t* status, uint8_t* out_g_c48,
+                           uint8_t* out_plain, int32_t* inst_status);
+
 /* SecretKey::decrypt for n ciphertexts (u_i, v_i, w_i) under ONE secret key (32-byte LE scalar):
  * the row / value a node decrypts from every SyncKeyGen Part and Ack (src/sync_key_gen.rs:358,
  * 481-484; 10^6 Acks per era at N = 1000).  Per item: H = hash_g1_g2(u, v) (host candidates, GPU
- * cofactor clearing), Ciphertext::verify e(G1, w) == e(u, H) and g = sk u on the GPU, then
- * out = v XOR hash_bytes(g, |v|) on the host's cores.  v_i = msgs[offsets[i] .. offsets[i+1]),
+ * cofactor clearing), Ciphertext::verify e(G1, w) == e(u, H), g = sk u and
+ * out = v XOR hash_bytes(g, |v|) on the GPU (H and g stay on the device).  v_i = msgs[offsets[i] .. offsets[i+1]),
  * out has the same layout.  status[i] = ACCEPT (decrypted), REJECT (Ciphertext::verify failed:
  * decrypt returns None, Fault::ValueDecryption), DECODE_ERR (u or w does not decode). */
 int hbtc_decrypt(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const uint8_t* u_c48,
@@ -259,6 +281,17 @@ int hbtc_dec_epoch_submit(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_ct, cons
                           const uint8_t* w_c96, const uint32_t* offsets, const uint32_t* idx,
                           const uint8_t* share_c48, uint32_t t, int32_t* status, uint8_t* out_g_c48,
                           int32_t* inst_status, uint64_t* ticket);
+/* hbtc_dec_epoch_submit plus the plaintexts (as hbtc_threshold_decrypt, pipelined): v is staged in
+ * the lane's pinned input with the shares, the seed and the pad follow the combine on the lane's
+ * stream, and the plaintexts come back through the lane's pinned output, copied to out_plain by
+ * hbtc_wait (or by the submit that retires the ticket).  The same four-in-flight rule.  t >= 1
+ * (t == 0: HBTC_ERR_ARG); out_g_c48 may be NULL. */
+int hbtc_dec_epoch_submit_plain(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_ct,
+                                const uint8_t* H_c96, const uint8_t* w_c96, const uint32_t* offsets,
+                                const uint32_t* idx, const uint8_t* share_c48, uint32_t t,
+                                const uint8_t* v, const uint32_t* v_offsets, int32_t* status,
+                                uint8_t* out_g_c48, uint8_t* out_plain, int32_t* inst_status,
+                                uint64_t* ticket);
 int hbtc_sig_epoch_submit(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H_c96,
                           const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_c96,
                           uint32_t t, int32_t* status, uint8_t* out_sig_c96, uint8_t* out_parity,
@@ -323,6 +356,17 @@ int hbtc_combine_sigs_verified_dev(hbtc_ctx* ctx, uint32_t n_inst, const uint32_
                                    const uint32_t* d_idx, const uint8_t* d_sig_c96,
                                    const int32_t* d_status, uint32_t t, uint8_t* d_out_sig_c96,
                                    uint8_t* d_out_parity, int32_t* d_inst_status);
+
+/* The pad behind a combine, for callers that hold g on the device: d_out[v_offsets[k] ..
+ * v_offsets[k+1]) = d_v[same range] XOR hash_bytes(g_k, len) for the n items whose d_gate_status[k]
+ * is HBTC_ACCEPT (NULL: every item), zeros for the others.  d_g_c48 (16-byte aligned) and
+ * d_gate_status are typically the d_out_g_c48 / d_inst_status of a hbtc_combine_dec*_dev call on
+ * this context: the call is ordered after any pending combine that writes them, on the stream that
+ * combine ran on, with no host synchronisation.  v_offsets is a HOST array (offsets[0] == 0,
+ * non-decreasing, the pad-block limit of hbtc_encrypt); d_v and d_out may not overlap. */
+int hbtc_pad_xor_dev(hbtc_ctx* ctx, uint32_t n, const uint8_t* d_g_c48,
+                     const int32_t* d_gate_status, const uint32_t* v_offsets, const uint8_t* d_v,
+                     uint8_t* d_out);
 
 /* ---- commitments ------------------------------------------------------------------------ */
 /* Commitment::evaluate(x) for n_x points at once: out_k = sum_j xs[k]^j C_j over the n_coeff
@@ -558,7 +602,8 @@ int hbtc_merkle_validate_dev(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const 
  * Lagrange coefficients), "comb_decode", "comb_digits", "combine" (MSM bucket reduction), "skg_scalars", "skg_ack_rows",
  * "mul", "rlc_items", "chk_tiles", "chk_tiles_w", "chk_halves", "chk_halves_w", "chk_subs",
  * "chk_subs_w", "chk_leaves", "rlc_finalize", "rs", "merkle",
- * "merkle_validate".  Reading
+ * "merkle_validate", "dec_pad" (k_dec_seed + k_enc_pad behind a combine or hbtc_decrypt's
+ * multiplication).  Reading
  * synchronises the stream. */
 int hbtc_timing_enable(hbtc_ctx* ctx, int enable);
 int hbtc_timing_read(hbtc_ctx* ctx, const char* family, double* total_ms, uint64_t* launches);

@@ -10,6 +10,7 @@
 //!   Coin::try_output   -> combine_signatures + parity     combine_sigs        (src/coin.rs:185-191)
 //!   ThresholdDecryption -> verify_decryption_share        verify_dec_shares   (src/threshold_decryption.rs:159)
 //!   ThresholdDecryption -> PublicKeySet::decrypt          combine_dec         (src/threshold_decryption.rs:181-185)
+//!   ThresholdDecryption::try_output, to the plaintext     threshold_decrypt   (src/threshold_decryption.rs:164-188)
 //!   SyncKeyGen::handle_part / handle_ack                  skg_check_parts / skg_check_acks / decrypt
 //!   HoneyBadger::propose, SyncKeyGen::new / Ack values     encrypt / fr_poly_eval (src/sync_key_gen.rs:320-322,372-379)
 #![allow(clippy::too_many_arguments)]
@@ -231,6 +232,31 @@ impl Context {
                                   out.as_mut_ptr(), st.as_mut_ptr())
         })?;
         Ok((out, st))
+    }
+
+    /// One ThresholdDecryption round (try_output, src/threshold_decryption.rs:164-188): the shares of
+    /// `b` verified against (h, w), the first t ACCEPTed shares of every ciphertext combined and the
+    /// plaintext v ^ hash_bytes(g, |v|) made on the GPU.  v holds ciphertext k's v at
+    /// v_offsets[k] .. v_offsets[k + 1].  Returns (share status, g, plaintexts in v's layout,
+    /// ciphertext status); a ciphertext that is not ACCEPT has zeros for g and for its plaintext.
+    pub fn threshold_decrypt(&self, keyset: u32, h_c96: &[u8], w_c96: &[u8], b: &Batch, t: u32, v: &[u8],
+                             v_offsets: &[u32]) -> Result<(Vec<i32>, Vec<u8>, Vec<u8>, Vec<i32>)> {
+        b.check(48);
+        let n = b.n_inst() as usize;
+        assert_eq!(h_c96.len(), 96 * n, "one compressed G2 H per ciphertext");
+        assert_eq!(w_c96.len(), 96 * n, "one compressed G2 w per ciphertext");
+        assert!(t >= 1, "t must be >= 1");
+        assert_eq!(v_offsets.len(), n + 1, "one v per ciphertext");
+        assert!(v_offsets[0] == 0 && v_offsets.windows(2).all(|w| w[0] <= w[1]), "v_offsets must start at 0 and not decrease");
+        assert!(v_offsets[n] as usize <= v.len(), "v_offsets past the bytes of v");
+        let (mut st, mut g) = (vec![0i32; b.idx.len()], vec![0u8; 48 * n]);
+        let (mut plain, mut cst) = (vec![0u8; v.len()], vec![0i32; n]);
+        self.ok(unsafe {
+            ffi::hbtc_threshold_decrypt(self.raw, keyset, b.n_inst(), h_c96.as_ptr(), w_c96.as_ptr(), b.offsets.as_ptr(),
+                                        b.idx.as_ptr(), b.items.as_ptr(), t, v.as_ptr(), v_offsets.as_ptr(),
+                                        st.as_mut_ptr(), g.as_mut_ptr(), plain.as_mut_ptr(), cst.as_mut_ptr())
+        })?;
+        Ok((st, g, plain, cst))
     }
 
     /// SecretKey::decrypt for a batch under one key: (plaintexts in the msgs layout, status).

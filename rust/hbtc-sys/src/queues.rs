@@ -340,14 +340,29 @@ struct TdState<N> {
 
 /// Every ThresholdDecryption instance (`src/threshold_decryption.rs:45`) of one epoch.  Output:
 /// the combined point g = sum l_i d_i (compressed G1); plaintext = v ^ hash_bytes(g, |v|).
+/// With `with_plaintext(true)` the flush's combines go through ONE `Context::threshold_decrypt`
+/// call (shares -> g -> plaintext on the device, the shares verified once more) and the bytes
+/// try_output returns (td.rs:187) are kept per instance for `take_plaintext`.
 pub struct DecryptionEpoch<K: Ord + Clone, N: Ord + Clone> {
     ni: NetInfo<N>,
     inst: BTreeMap<K, TdState<N>>,
+    plaintext: bool,
+    plaintexts: BTreeMap<K, Vec<u8>>,
 }
 
 impl<K: Ord + Clone, N: Ord + Clone> DecryptionEpoch<K, N> {
     pub fn new(ni: NetInfo<N>) -> Self {
-        DecryptionEpoch { ni, inst: BTreeMap::new() }
+        DecryptionEpoch { ni, inst: BTreeMap::new(), plaintext: false, plaintexts: BTreeMap::new() }
+    }
+
+    pub fn with_plaintext(mut self, on: bool) -> Self {
+        self.plaintext = on;
+        self
+    }
+
+    /// The plaintext of an instance that output in an earlier flush (plaintext mode), once.
+    pub fn take_plaintext(&mut self, key: &K) -> Option<Vec<u8>> {
+        self.plaintexts.remove(key)
     }
 
     pub fn add(&mut self, key: K, our_share_c48: Option<[u8; 48]>) {
@@ -450,8 +465,28 @@ impl<K: Ord + Clone, N: Ord + Clone> DecryptionEpoch<K, N> {
             let offsets = csr(&counts);
             let idx: Vec<u32> = pending.iter().flat_map(|p| p.2.iter().map(|(i, _)| *i)).collect();
             let sh: Vec<u8> = pending.iter().flat_map(|p| p.2.iter().flat_map(|(_, s)| s.iter().copied())).collect();
-            let (g, cst) = ctx.combine_dec(&Batch { offsets: &offsets, idx: &idx, items: &sh }, t)?;
+            let batch = Batch { offsets: &offsets, idx: &idx, items: &sh };
+            let mut plain: Vec<u8> = Vec::new();
+            let mut v_off: Vec<u32> = vec![0];
+            let (g, cst) = if self.plaintext {
+                let (mut hs, mut ws, mut vs) = (Vec::new(), Vec::new(), Vec::new());
+                for p in &pending {
+                    let ct = self.inst[&p.0].ct.as_ref().expect("a terminated instance has its ciphertext");
+                    hs.extend_from_slice(&ct.h);
+                    ws.extend_from_slice(&ct.w);
+                    vs.extend_from_slice(&ct.v);
+                    v_off.push(vs.len() as u32);
+                }
+                let (_, g, p, cst) = ctx.threshold_decrypt(self.ni.keyset, &hs, &ws, &batch, t, &vs, &v_off)?;
+                plain = p;
+                (g, cst)
+            } else {
+                ctx.combine_dec(&batch, t)?
+            };
             for (j, (k, e, _)) in pending.into_iter().enumerate() {
+                if self.plaintext && cst[j] == ACCEPT {
+                    self.plaintexts.insert(k.clone(), plain[v_off[j] as usize..v_off[j + 1] as usize].to_vec());
+                }
                 let step: &mut Step<N, [u8; 48]> = &mut results.get_mut(&k).unwrap()[e];
                 if cst[j] == ACCEPT {
                     let mut out = [0u8; 48];
