@@ -20,7 +20,7 @@ SKG_PARTS := 10
 KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_PARTS),$(BUILD)/hbtc_rlc.p$(p).o) \
          $(foreach p,$(MSM_PARTS),$(BUILD)/hbtc_msm.p$(p).o) $(foreach p,$(SKG_PARTS),$(BUILD)/hbtc_skg.p$(p).o) \
          $(BUILD)/hbtc_check.c1.o $(BUILD)/hbtc_check.c2.o $(BUILD)/hbtc_sig.s1.o $(BUILD)/hbtc_sig.s2.o $(BUILD)/hbtc_pb.o \
-         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o
+         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o
 LIB := hbbft_amd/libhbtc.so
 
 .PHONY: all lib hosttest devtest oracle clean resources roofline-constants
@@ -107,6 +107,11 @@ $(BUILD)/hbtc_comb.o: $(CSRC)/hbtc_comb.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_enc.o: $(CSRC)/hbtc_enc.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
 
+# SyncKeyGen::generate + NetworkInfo::new (column sum, Fr interpolation, commitment evaluation by
+# Horner): the flag set of hbtc_enc.o (`make resources-keygen` prints the resource report)
+$(BUILD)/hbtc_keygen.o: $(CSRC)/hbtc_keygen.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
+
 # Reliable Broadcast: Reed-Solomon over GF(2^8), SHA3 Merkle trees and proofs
 $(BUILD)/hbtc_bcast.o: $(CSRC)/hbtc_bcast.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -135,7 +140,23 @@ resources-enc:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
 
-hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so
+.PHONY: resources-keygen
+resources-keygen:
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_keygen.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
+
+hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
+          tests/native/libhbtc_keygen_hosttest.so
+tests/native/libhbtc_keygen_hosttest.so: tests/native/hbtc_keygen_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_keygen_hosttest.cpp -o $@
+# keygen.h's host build (the column sum, the interpolation at 0 over its 256 simulated lanes, the
+# Horner evaluation, the shared-inversion affine conversion) as a stand-alone program under
+# AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-keygen
+sanitize-keygen: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_keygen_host_main.cpp tests/native/hbtc_keygen_hosttest.cpp -o $(BUILD)/keygen_host_asan
+	$(BUILD)/keygen_host_asan
 tests/native/libhbtc_dec_hosttest.so: tests/native/hbtc_dec_hosttest.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_dec_hosttest.cpp -o $@
 tests/native/libhbtc_enc_hosttest.so: tests/native/hbtc_enc_hosttest.cpp $(HDRS)

@@ -35,6 +35,12 @@ checked against the construction after timing:
       Parts (N evaluations and N encryptions each, :371-380).  Host buffers and the Python
       framing are inside the timed region; sampled recipients decrypt their row and values after
       timing and check them against the commitment and the rows.
+  kg  The end of a SyncKeyGen era at N = --nodes, t = (N - 1) / 3 (not in the default list): one
+      generate_keys() of hbbft_amd/skg.py over t + 1 complete Parts of t + 1 values each
+      (SyncKeyGen::generate + NetworkInfo::new, src/sync_key_gen.rs:428-447, messaging.rs:253-256;
+      hbtc_skg_generate): the commitment, our secret key share, the N public key shares and the
+      loaded key set, checked against the construction before timing.  --kg-parent also times,
+      once, the calls it replaced for the same inputs (the Python interpolation on 32 Parts, scaled).
   td  One ThresholdDecryption epoch to the PLAINTEXT, C3-shaped (N = --nodes, N ciphertexts,
       t = f + 1; 10^6 shares at N = 1000), contributions of --td-bytes each (not in the default
       list).  Three paths over the same host inputs, interleaved per repeat: (a)
@@ -52,7 +58,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,bc,td] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -82,7 +88,7 @@ G2_GEN = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bb
                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
 SEED = 0x6862626674
 N_OUT = 6  # output sets rotated per step (bench.py's N_OUT)
-STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5}
+STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5, "kg": 3}
 
 
 def log(*a):
@@ -791,6 +797,108 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
     }
 
 
+def bench_keygen(ctx, n, steps, warmup, parent=False):
+    """kg: the end of a SyncKeyGen era at N=n (t = (n-1)/3) through hbbft_amd/skg.py as a caller uses
+    it: one generate_keys() over t + 1 complete Parts of t + 1 values each (SyncKeyGen::generate +
+    NetworkInfo::new: commitment, secret key share, n public key shares, the key set loaded).  The
+    results are checked against the construction (known scalars) before timing.  parent=True also
+    times, once, the path the call replaced for the same inputs: hbtc_g1_msm with all-ones scalars,
+    the Python Lagrange interpolation (on 32 of the Parts, scaled), hbtc_commitment_evaluate,
+    hbtc_keyset_load and hbtc_keyset_set_master."""
+    from hbbft_amd import skg
+    rng = random.Random(SEED + 77)
+    t = (n - 1) // 3
+    t1, n_parts = t + 1, t + 1
+    sc = [[rng.randrange(R) for _ in range(t1)] for _ in range(n_parts)]
+    pts, st = ctx.g1_mul(G1_GEN, fr_bytes([c for r in sc for c in r]))
+    assert not st.any()
+    pts = bytes(pts)
+    polys = [[rng.randrange(R) for _ in range(t1)] for _ in range(n_parts)]
+    vals = ctx.fr_poly_eval(polys, list(range(1, t1 + 1)))  # [part, x - 1, 32]
+    pub = {i: G1_GEN for i in range(n)}
+    kg = skg.SyncKeyGen(ctx, 17 % n, 1, pub, t)
+    for p in range(n_parts):
+        # only row 0 of the bivariate commitment is read: a sparse stand-in for the packed list
+        prop = skg._Proposal({skg.coeff_pos(0, j): pts[48 * (p * t1 + j):48 * (p * t1 + j) + 48]
+                              for j in range(t1)})
+        prop.values = {x: int.from_bytes(vals[p, x - 1].tobytes(), "little") for x in range(1, t1 + 1)}
+        prop.acks = set(range(2 * t + 1))
+        kg.parts[p] = prop
+    # the construction's answers
+    s = [sum(r[j] for r in sc) % R for j in range(t1)]
+
+    def at(x):
+        acc = 0
+        for c in reversed(s):
+            acc = (acc * x + c) % R
+        return acc
+    sks = [at(i + 1) for i in range(n)]
+    want, st = ctx.g1_mul(G1_GEN, fr_bytes(s + sks))
+    assert not st.any()
+    want = bytes(want)
+    want_commit = [want[48 * j:48 * j + 48] for j in range(t1)]
+    want_pks = [want[48 * (t1 + i):48 * (t1 + i) + 48] for i in range(n)]
+    want_sk = sum(f[0] for f in polys) % R
+    commit, sk, pks, kid = kg.generate_keys()
+    bad = (commit != want_commit) + (pks != want_pks) + (sk != want_sk)
+    H = N.hash_g2(b"bench kg")
+    sample = sorted(set([0, n - 1] + [rng.randrange(n) for _ in range(6)]))
+    sig, st = ctx.g2_mul(H, [sks[i] for i in sample])
+    vst = ctx.verify_sig_shares(kid, [H], [len(sample)], sample, sig)
+    bad += int((vst != N.ACCEPT).sum())
+    ctx.keyset_free(kid)
+    if bad:
+        raise SystemExit("kg: %d results differ from the construction" % bad)
+
+    def step():
+        _, _, _, k = kg.generate_keys()
+        ctx.keyset_free(k)
+
+    elapsed = timed_steps(ctx, step, steps, warmup)
+    per = breakdown(ctx, steps, ["keygen", "keygen_sum", "keygen_sk", "keygen_shares", "prepare"])
+    out = {
+        "metric": "SyncKeyGen generate + NetworkInfo::new: ms per era (commitment, secret share, N key shares, key set loaded)",
+        "value": round(elapsed / steps * 1e3, 3), "unit": "ms per generate_keys()",
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
+        "higher_is_better": False, "dtype": "u32 (381-bit / 255-bit Montgomery limbs)",
+        "data": "synthetic (random row-0 scalars, values on random degree-t polynomials); host buffers "
+                "(PCIe-inclusive), Python marshalling and keyset_free included",
+        "config": {"workload": "kg: SyncKeyGen N=%d: %d complete Parts of %d values, %d key shares"
+                   % (n, n_parts, t1, n), "N": n, "t": t, "parts": n_parts},
+        "kernel_event_spans_ms_per_step": per, "mismatches": bad,
+    }
+    if parent:
+        done = [kg.parts[p] for p in sorted(kg.parts)]
+        a0 = time.perf_counter()
+        by_col = [st_.commit[skg.coeff_pos(0, j)] for j in range(t1) for st_ in done]
+        old_commit, mst = ctx.g1_msm(t1, len(done), by_col, [1] * len(by_col))
+        a1 = time.perf_counter()
+        n_int = min(32, len(done))
+        part_sk = 0
+        for st_ in done[:n_int]:
+            part_sk = (part_sk + skg._lagrange_at_zero(sorted(st_.values.items())[:t1])) % R
+        a2 = time.perf_counter()
+        old_pks, est = ctx.commitment_evaluate(old_commit, [i + 1 for i in range(n)])
+        a3 = time.perf_counter()
+        k_old, n_bad = ctx.keyset_load(old_pks)
+        ctx.keyset_set_master(k_old, old_commit[0])
+        a4 = time.perf_counter()
+        ctx.keyset_free(k_old)
+        same = (not mst.any() and not est.any() and old_commit == commit and old_pks == pks and n_bad == 0
+                and part_sk == sum(f[0] for f in polys[:n_int]) % R)
+        interp = (a2 - a1) * len(done) / n_int
+        out["parent_ms"] = {
+            "commitment_sum_g1_msm": round((a1 - a0) * 1e3, 1),
+            "secret_share_python": round(interp * 1e3, 1),
+            "secret_share_python_measured_parts": n_int,
+            "key_shares_commitment_evaluate": round((a3 - a2) * 1e3, 1),
+            "keyset_load_and_set_master": round((a4 - a3) * 1e3, 1),
+            "total": round(((a1 - a0) + interp + (a4 - a2)) * 1e3, 1),
+            "same_results": bool(same),
+        }
+    return out
+
+
 def bench_threshold_decrypt(ctx, n, v_bytes, steps, warmup, corrupt):
     """td: one ThresholdDecryption epoch to the plaintext (see the docstring): n ciphertexts of
     v_bytes, n shares each (a fraction `corrupt` wrong), t = f + 1."""
@@ -1014,7 +1122,10 @@ def main():
                     help="c2 / c4: explicit device slots of the node, e.g. 0,0 (two contexts on GPU 0: "
                          "a rehearsal of the node path on one GPU)")
     ap.add_argument("--parts", type=int, default=1000, help="c5 / c5p Parts (c5p: at most --nodes)")
-    ap.add_argument("--nodes", type=int, default=1000, help="c5p / td: N")
+    ap.add_argument("--nodes", type=int, default=1000, help="c5p / td / kg: N")
+    ap.add_argument("--kg-parent", action="store_true",
+                    help="kg: also time, once, the calls generate_keys() replaced (Python interpolation "
+                         "on 32 Parts, scaled)")
     ap.add_argument("--distinct", type=int, default=4, help="c5 distinct bivariate polynomials")
     ap.add_argument("--td-bytes", type=int, default=1024, help="td: bytes per contribution")
     ap.add_argument("--bc-value", type=int, default=65536, help="bc: bytes per proposed value")
@@ -1034,7 +1145,7 @@ def main():
     try:
         for c in args.configs.split(","):
             steps = args.steps if args.steps is not None else STEPS_DEFAULT.get(c, 2)
-            warmup = args.warmup if args.warmup is not None else (1 if c in ("c5", "c5p") else 2)
+            warmup = args.warmup if args.warmup is not None else (1 if c in ("c5", "c5p", "kg") else 2)
             if c == "c1":
                 out = bench_c1(ctx, steps, warmup, cpu_budget=0.0 if args.no_cpu else 10.0)
             elif c == "c2":
@@ -1048,6 +1159,8 @@ def main():
                 out = bench_broadcast(ctx, 256, args.bc_value, steps, warmup)
             elif c == "td":
                 out = bench_threshold_decrypt(ctx, args.nodes, args.td_bytes, steps, warmup, args.corrupt)
+            elif c == "kg":
+                out = bench_keygen(ctx, args.nodes, steps, warmup, parent=args.kg_parent)
             elif c == "c5p":
                 out = bench_skg_producer(ctx, args.nodes, min(args.parts, args.nodes), steps, warmup)
             elif c == "c5":

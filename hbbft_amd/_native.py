@@ -120,6 +120,7 @@ SIGNATURES = {
     "hbtc_decrypt": (_I32, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "hbtc_encrypt": (_I32, [_P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "hbtc_fr_poly_eval": (_I32, [_P, _U32, _U32, _P, _U32, _P, _P]),
+    "hbtc_skg_generate": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "hbtc_unframe_points_dev": (_I32, [_P, _U32, _U32, _P, _P]),
     "hbtc_stream_wait_ctx": (_I32, [_P, _P]),
     "hbtc_ctx_wait_stream": (_I32, [_P, _P]),
@@ -812,6 +813,47 @@ class Context:
         self._check(self.lib.hbtc_fr_poly_eval(self.h, n_poly, n_coeff, _ptr(cb), n_x, _ptr(xb),
                                                _ptr(out)), "hbtc_fr_poly_eval")
         return out.reshape(n_poly, n_x, 32)
+
+    # ---- SyncKeyGen::generate + NetworkInfo::new
+    def skg_generate(self, t, row0, values, n_nodes, load_keyset=False, want_shares=True):
+        """hbtc_skg_generate.  row0: per complete Part its t + 1 compressed coefficients (0, j) (a
+        list of lists, or one packed buffer).  values: per Part a list of (x, value) pairs in the
+        order they are stored (x = sender index + 1; ints, any value below 2^256), or None for an
+        observer.  Returns (commit [t + 1 x 48 B], sk int or None, pk_shares [n_nodes x 48 B] or
+        None, keyset id or None, status); on a status other than ACCEPT the outputs are
+        zero-filled, sk is 0 / None and there is no key set."""
+        t1 = int(t) + 1
+        if isinstance(row0, (list, tuple)) and row0 and isinstance(row0[0], (list, tuple)):
+            if any(len(r) != t1 for r in row0):
+                raise ValueError("t + 1 points per Part")
+            row0 = [p for r in row0 for p in r]
+        rb = _join(row0, 48)
+        if rb.size % (48 * t1):
+            raise ValueError("t + 1 points per Part")
+        n_parts = rb.size // (48 * t1)
+        off = xs = vb = sk = None
+        if values is not None:
+            if len(values) != n_parts:
+                raise ValueError("one list of values per Part")
+            off = _offsets([len(v) for v in values], False)
+            xs = np.ascontiguousarray([x for v in values for x, _ in v], dtype=np.uint32)
+            flat = [int(y) for v in values for _, y in v]
+            vb = np.frombuffer(b"".join(y.to_bytes(32, "little") for y in flat), np.uint8).copy() \
+                if flat else np.zeros(0, np.uint8)
+            sk = np.zeros(32, np.uint8)
+        commit = np.zeros(48 * t1, np.uint8)
+        pks = np.zeros(48 * n_nodes, np.uint8) if (want_shares and n_nodes) else None
+        kid, st = _U32(0xFFFFFFFF), _I32(-1)
+        self._check(self.lib.hbtc_skg_generate(
+            self.h, n_parts, int(t), _ptr(rb), _ptr(off), _ptr(xs), _ptr(vb), int(n_nodes), _ptr(commit),
+            _ptr(pks), _ptr(sk), ctypes.byref(kid) if load_keyset else None, ctypes.byref(st)),
+            "hbtc_skg_generate")
+        cb = commit.tobytes()
+        pb = pks.tobytes() if pks is not None else None
+        return ([cb[48 * j:48 * j + 48] for j in range(t1)],
+                int.from_bytes(sk.tobytes(), "little") if sk is not None else None,
+                [pb[48 * i:48 * i + 48] for i in range(n_nodes)] if pb is not None else None,
+                kid.value if load_keyset and st.value == ACCEPT else None, st.value)
 
     # ---- commitments
     def commitment_evaluate(self, commit, xs):

@@ -1628,6 +1628,62 @@ struct Guard {
   explicit Guard(hbtc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
 };
 
+// ---- key sets: the steps hbtc_keyset_load and hbtc_skg_generate share
+void keyset_release(Keyset& ks) {
+  (void)hipFree(ks.pk);
+  (void)hipFree(ks.st);
+  (void)hipFree(ks.tab);
+  (void)hipFree(ks.last_bad);
+  (void)hipFree(ks.rejects);
+  (void)hipFree(ks.master);
+  ks = Keyset();
+}
+
+// The decoded shares and their statuses, filled by the caller's work on the stream (a decode of
+// uploaded bytes, or the key generation's affine conversion).
+int keyset_alloc_shares(hbtc_ctx* c, Keyset& ks, uint32_t n) {
+  ks.n = n;
+  HB_CHECK(c, hipMalloc(&ks.pk, sizeof(G1A) * n));
+  HB_CHECK(c, hipMalloc(&ks.st, sizeof(int32_t) * n));
+  return HBTC_OK;
+}
+
+// Everything behind the decoded shares: the sender-tracking arrays and the fixed-base tables,
+// enqueued after the work that fills ks.pk / ks.st.
+int keyset_tables(hbtc_ctx* c, Keyset& ks) {
+  const uint32_t n = ks.n;
+  HB_CHECK(c, hipMalloc(&ks.tab, sizeof(PtXY) * (size_t)n * PK_TAB_WIN * 256));
+  HB_CHECK(c, hipMalloc(&ks.last_bad, sizeof(uint32_t) * n));
+  HB_CHECK(c, launch_zero_u32(c->stream, ks.last_bad, n));
+  HB_CHECK(c, hipMalloc(&ks.rejects, hbtc_ctx::NL * sizeof(uint32_t) * n));  // one count array per lane
+  HB_CHECK(c, launch_zero_u32(c->stream, ks.rejects, hbtc_ctx::NL * (size_t)n));
+  Fq* tab_ws;
+  HB_TRY(wst(c, "pktab.ws", (size_t)n * PK_TAB_WIN * 512, &tab_ws));
+  return timed(c, "prepare", [&] { return launch_pk_table(c->stream, ks.pk, ks.st, n, ks.tab, tab_ws); });
+}
+
+uint32_t keyset_register(hbtc_ctx* c, const Keyset& ks) {
+  const uint32_t id = c->next_keyset++;
+  c->keysets[id] = ks;
+  return id;
+}
+
+// One timing span over several launches (timed_on covers one launch expression).
+int span_begin(hbtc_ctx* c, Span& sp) {
+  if (!c->timing) return HBTC_OK;
+  HB_CHECK(c, hipEventCreate(&sp.a));
+  HB_CHECK(c, hipEventCreate(&sp.b));
+  HB_CHECK(c, hipEventRecord(sp.a, c->stream));
+  return HBTC_OK;
+}
+int span_end(hbtc_ctx* c, Span& sp, const char* family) {
+  if (!c->timing) return HBTC_OK;
+  HB_CHECK(c, hipEventRecord(sp.b, c->stream));
+  sp.family = family;
+  c->spans.push_back(sp);
+  return HBTC_OK;
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1797,33 +1853,26 @@ int hbtc_keyset_load(hbtc_ctx* c, const uint8_t* pk_c48, uint32_t n, uint32_t* k
   if (!c || !pk_c48 || !keyset_id || n == 0) return HBTC_ERR_ARG;
   Guard g(c);
   Keyset ks;
-  ks.n = n;
-  HB_CHECK(c, hipMalloc(&ks.pk, sizeof(G1A) * n));
-  HB_CHECK(c, hipMalloc(&ks.st, sizeof(int32_t) * n));
-  void* d_in;
-  HB_TRY(upload(c, "in0", pk_c48, (size_t)48 * n, &d_in));
-  HB_TRY(timed(c, "prepare", [&] {
-    return launch_g1_decode(c->stream, (const uint8_t*)d_in, n, ks.pk, ks.st);
-  }));
-  HB_CHECK(c, hipMalloc(&ks.tab, sizeof(PtXY) * (size_t)n * PK_TAB_WIN * 256));
-  HB_CHECK(c, hipMalloc(&ks.last_bad, sizeof(uint32_t) * n));
-  HB_CHECK(c, launch_zero_u32(c->stream, ks.last_bad, n));
-  HB_CHECK(c, hipMalloc(&ks.rejects, hbtc_ctx::NL * sizeof(uint32_t) * n));  // one count array per lane
-  HB_CHECK(c, launch_zero_u32(c->stream, ks.rejects, hbtc_ctx::NL * (size_t)n));
-  Fq* tab_ws;
-  HB_TRY(wst(c, "pktab.ws", (size_t)n * PK_TAB_WIN * 512, &tab_ws));
-  HB_TRY(timed(c, "prepare", [&] {
-    return launch_pk_table(c->stream, ks.pk, ks.st, n, ks.tab, tab_ws);
-  }));
   std::vector<int32_t> st(n);
-  HB_TRY(download(c, st.data(), ks.st, sizeof(int32_t) * n));
-  HB_TRY(sync(c));
+  const int rc = [&]() -> int {
+    HB_TRY(keyset_alloc_shares(c, ks, n));
+    void* d_in;
+    HB_TRY(upload(c, "in0", pk_c48, (size_t)48 * n, &d_in));
+    HB_TRY(timed(c, "prepare", [&] {
+      return launch_g1_decode(c->stream, (const uint8_t*)d_in, n, ks.pk, ks.st);
+    }));
+    HB_TRY(keyset_tables(c, ks));
+    HB_TRY(download(c, st.data(), ks.st, sizeof(int32_t) * n));
+    return sync(c);
+  }();
+  if (rc != HBTC_OK) {
+    keyset_release(ks);
+    return rc;
+  }
   uint32_t bad = 0;
   for (uint32_t i = 0; i < n; ++i) bad += st[i] != HBTC_ACCEPT;
   if (n_bad) *n_bad = bad;
-  const uint32_t id = c->next_keyset++;
-  c->keysets[id] = ks;
-  *keyset_id = id;
+  *keyset_id = keyset_register(c, ks);
   return HBTC_OK;
 }
 
@@ -1833,12 +1882,7 @@ int hbtc_keyset_free(hbtc_ctx* c, uint32_t keyset_id) {
   auto it = c->keysets.find(keyset_id);
   if (it == c->keysets.end()) return fail(c, HBTC_ERR_NO_KEYSET, "unknown keyset id");
   HB_TRY(sync(c));
-  (void)hipFree(it->second.pk);
-  (void)hipFree(it->second.st);
-  (void)hipFree(it->second.tab);
-  (void)hipFree(it->second.last_bad);
-  (void)hipFree(it->second.rejects);
-  (void)hipFree(it->second.master);
+  keyset_release(it->second);
   c->keysets.erase(it);
   return HBTC_OK;
 }
@@ -3501,6 +3545,137 @@ int hbtc_fr_poly_eval(hbtc_ctx* c, uint32_t n_poly, uint32_t n_coeff, const uint
   }));
   HB_TRY(download(c, out_le32, d_out, (size_t)n_out * 32));
   return sync(c);
+}
+
+// hbtc.h hbtc_skg_generate: one packed upload, the stages of hbtc_keygen.hip back to back on the
+// stream (the key set's tables behind them), one packed download, one wait.
+int hbtc_skg_generate(hbtc_ctx* c, uint32_t n_parts, uint32_t t, const uint8_t* row0_c48,
+                      const uint32_t* val_offsets, const uint32_t* val_x, const uint8_t* vals_le32,
+                      uint32_t n_nodes, uint8_t* out_commit_c48, uint8_t* out_pk_shares_c48,
+                      uint8_t* out_sk_le32, uint32_t* out_keyset_id, int32_t* status) {
+  if (!c || n_parts == 0 || !row0_c48 || !out_commit_c48 || !status || t == 0xffffffffu)
+    return HBTC_ERR_ARG;
+  if ((val_offsets == nullptr) != (out_sk_le32 == nullptr)) return HBTC_ERR_ARG;
+  if (out_keyset_id && n_nodes == 0) return HBTC_ERR_ARG;
+  Guard g(c);
+  const uint32_t t1 = t + 1;
+  const uint64_t n_pts64 = (uint64_t)n_parts * t1;
+  if (n_pts64 > (1ull << 26) || (uint64_t)n_nodes * kg_segment_count(t1) > (1ull << 26))
+    return fail(c, HBTC_ERR_ARG, "skg_generate: more than 2^26 commitment points or key-share segments");
+  const uint32_t n_pts = (uint32_t)n_pts64;
+  uint32_t n_vals = 0;
+  if (val_offsets) {
+    HB_TRY(check_offsets(c, n_parts, val_offsets, &n_vals));
+    for (uint32_t p = 0; p < n_parts; ++p)
+      if (val_offsets[p + 1] - val_offsets[p] > t1)
+        return fail(c, HBTC_ERR_ARG, "skg_generate: a Part holds more than t + 1 values");
+    if (n_vals && (!val_x || !vals_le32)) return fail(c, HBTC_ERR_ARG, "skg_generate: NULL value array");
+    for (uint32_t i = 0; i < n_vals; ++i)
+      if (val_x[i] == 0) return fail(c, HBTC_ERR_ARG, "skg_generate: x == 0");
+  }
+  auto pad16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  // the packed input: row0 | val_offsets | val_x | vals
+  const size_t in_off = pad16((size_t)48 * n_pts), in_x = in_off + pad16((size_t)4 * (n_parts + 1)),
+               in_vals = in_x + pad16((size_t)4 * n_vals), in_bytes = in_vals + (size_t)32 * n_vals;
+  std::vector<uint8_t> h_in(in_bytes, 0);
+  memcpy(h_in.data(), row0_c48, (size_t)48 * n_pts);
+  if (val_offsets) {
+    memcpy(h_in.data() + in_off, val_offsets, (size_t)4 * (n_parts + 1));
+    if (n_vals) {
+      memcpy(h_in.data() + in_x, val_x, (size_t)4 * n_vals);
+      memcpy(h_in.data() + in_vals, vals_le32, (size_t)32 * n_vals);
+    }
+  }
+  // the packed output: commit | pk shares | sk | flags
+  const size_t o_pk = pad16((size_t)48 * t1), o_sk = o_pk + pad16((size_t)48 * n_nodes), o_flags = o_sk + 32,
+               out_bytes = o_flags + 16;
+  std::vector<uint8_t> h_out(out_bytes, 0);
+  const uint32_t n_seg = kg_segment_count(t1);
+  Keyset ks;
+  const int rc = [&]() -> int {
+    void* d_in_v;
+    uint8_t *d_in, *d_out;
+    G1A *d_dec, *d_caff;
+    G1J *d_col, *d_seg;
+    Fr *d_frws, *d_part;
+    HB_TRY(wst(c, "kg.out", out_bytes, &d_out));
+    HB_TRY(wst(c, "kg.dec", (size_t)n_pts, &d_dec));
+    HB_TRY(wst(c, "kg.col", (size_t)t1, &d_col));
+    HB_TRY(wst(c, "kg.caff", (size_t)t1, &d_caff));
+    HB_TRY(wst(c, "kg.seg", (size_t)n_seg * n_nodes, &d_seg));
+    HB_TRY(wst(c, "kg.frws", (size_t)5 * n_vals, &d_frws));
+    HB_TRY(wst(c, "kg.part", (size_t)n_parts, &d_part));
+    if (out_keyset_id) {
+      HB_TRY(keyset_alloc_shares(c, ks, n_nodes));
+      HB_CHECK(c, hipMalloc(&ks.master, sizeof(G1A)));
+    }
+    HB_TRY(upload(c, "kg.in", h_in.data(), in_bytes, &d_in_v));
+    d_in = static_cast<uint8_t*>(d_in_v);
+    uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + o_flags);
+    HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_out + o_sk), (32 + 16) / 4));
+    Span whole;
+    HB_TRY(span_begin(c, whole));
+    HB_TRY(timed(c, "keygen_sum", [&] {
+      const hipError_t e = launch_kg_decode(c->stream, n_pts, d_in, d_dec, d_flags);
+      if (e != hipSuccess) return e;
+      return launch_kg_colsum(c->stream, n_parts, t1, d_dec, d_col);
+    }));
+    if (val_offsets)
+      HB_TRY(timed(c, "keygen_sk", [&] {
+        return launch_kg_fr(c->stream, n_parts, n_vals, reinterpret_cast<const uint32_t*>(d_in + in_off),
+                            reinterpret_cast<const uint32_t*>(d_in + in_x), d_in + in_vals, d_frws, d_part,
+                            d_flags, d_out + o_sk);
+      }));
+    // the flags are final here: the conversions below zero their outputs when one is raised
+    HB_TRY(timed(c, "keygen_sum", [&] {
+      return launch_kg_affine(c->stream, t1, 1, 0, d_col, d_flags, d_caff, nullptr, d_out);
+    }));
+    if (n_nodes && (out_pk_shares_c48 || out_keyset_id)) HB_TRY(timed(c, "keygen_shares", [&] {
+      const hipError_t e = launch_kg_horner(c->stream, n_nodes, t1, d_caff, d_seg);
+      if (e != hipSuccess) return e;
+      return launch_kg_affine(c->stream, n_nodes, n_seg, n_nodes, d_seg, d_flags, ks.pk, ks.st,
+                              out_pk_shares_c48 ? d_out + o_pk : nullptr);
+    }));
+    if (out_keyset_id) {
+      HB_TRY(keyset_tables(c, ks));
+      HB_CHECK(c, hipMemcpyAsync(ks.master, d_caff, sizeof(G1A), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HB_TRY(span_end(c, whole, "keygen"));
+    HB_TRY(download(c, h_out.data(), d_out, out_bytes));
+    // nothing of the values or the secret share stays on the device
+    if (val_offsets) {
+      if (n_vals) {
+        HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_in + in_vals), (size_t)8 * n_vals));
+        HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_frws), (size_t)40 * n_vals));
+      }
+      HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_part), (size_t)8 * n_parts));
+      HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_out + o_sk), 8));
+    }
+    return sync(c);
+  }();
+  auto wipe = [](std::vector<uint8_t>& v) {
+    volatile uint8_t* p = v.data();
+    for (size_t i = 0; i < v.size(); ++i) p[i] = 0;
+  };
+  wipe(h_in);
+  if (rc != HBTC_OK) {
+    wipe(h_out);
+    keyset_release(ks);
+    return rc;
+  }
+  uint32_t flags[2];
+  memcpy(flags, h_out.data() + o_flags, 8);
+  *status = flags[0] ? HBTC_DECODE_ERR : flags[1] ? HBTC_DUPLICATE_ENTRY : HBTC_ACCEPT;
+  memcpy(out_commit_c48, h_out.data(), (size_t)48 * t1);
+  if (out_pk_shares_c48) memcpy(out_pk_shares_c48, h_out.data() + o_pk, (size_t)48 * n_nodes);
+  if (out_sk_le32) memcpy(out_sk_le32, h_out.data() + o_sk, 32);
+  wipe(h_out);
+  if (*status != HBTC_ACCEPT) {
+    keyset_release(ks);
+  } else if (out_keyset_id) {
+    *out_keyset_id = keyset_register(c, ks);
+  }
+  return HBTC_OK;
 }
 
 }  // extern "C"

@@ -378,6 +378,25 @@ hipError_t launch_fr_to_mont(hipStream_t s, uint64_t n, const uint8_t* in_le32, 
 hipError_t launch_fr_poly_eval(hipStream_t s, uint32_t n_poly, uint32_t n_coeff, const Fr* coeffs,
                                uint32_t n_x, const Fr* xs, uint8_t* out_le32);
 
+// ---- SyncKeyGen::generate + NetworkInfo::new (hbtc_keygen.hip, arithmetic in keygen.h)
+// flags: two words, [0] raised by a row0 point that does not decode, [1] by an x repeated inside
+// one Part; the launchers that produce outputs zero them when either is raised
+hipError_t launch_kg_decode(hipStream_t s, uint32_t n, const uint8_t* in_c48, G1A* out, uint32_t* flags);
+// col[j] = sum_p dec[p * t1 + j] (Jacobian)
+hipError_t launch_kg_colsum(hipStream_t s, uint32_t n_parts, uint32_t t1, const G1A* dec, G1J* col);
+// point i = sum_{s < n_seg} in[s * stride + i] -> aff[i] / st[i] (either may be null) and its 48
+// compressed bytes (may be null; 16-byte aligned), one inversion per 256 points
+hipError_t launch_kg_affine(hipStream_t s, uint32_t n, uint32_t n_seg, uint32_t stride, const G1J* in,
+                            const uint32_t* flags, G1A* aff, int32_t* st, uint8_t* out_c48);
+// sk = sum_p L_p(0) (canonical, 32 bytes at out_sk_le32) through Part p's values [off[p], off[p + 1]);
+// ws: 5 * n_vals Fr, part: n_parts Fr
+hipError_t launch_kg_fr(hipStream_t s, uint32_t n_parts, uint32_t n_vals, const uint32_t* off,
+                        const uint32_t* x, const uint8_t* vals_le32, Fr* ws, Fr* part,
+                        uint32_t* flags, uint8_t* out_sk_le32);
+// seg[s * n_nodes + i] = segment s of sum_j (i + 1)^j C_j, scaled to its place
+uint32_t kg_segment_count(uint32_t t1);
+hipError_t launch_kg_horner(hipStream_t s, uint32_t n_nodes, uint32_t t1, const G1A* C, G1J* seg);
+
 // ---- Reliable Broadcast (hbtc_bcast.hip)
 hipError_t launch_gf_apply(hipStream_t s, uint32_t n_jobs, const uint32_t* jobs, uint8_t* shards,
                            uint64_t stride, uint32_t len, uint32_t n_out, const uint32_t* out_rows,

@@ -21,9 +21,11 @@ Verdicts depend only on the message and the stored commitment, never on later st
 replay reproduces the sequential outcomes exactly (tests/test_gpu_skg_protocol.py checks this
 against oracle/hbbft_rules.py's line-by-line restatement).
 
-Keys: ``generate`` (:428-447) sums row(0) of the complete Parts' commitments (one batched G1 MSM)
-and interpolates our secret share; ``public_key_shares`` is Commitment::evaluate(i + 1) for
-every node (hbtc_commitment_evaluate; NetworkInfo::new, src/messaging.rs:253-256).
+Keys: ``generate`` (:428-447) sums row(0) of the complete Parts' commitments and interpolates our
+secret share on the device (hbtc_skg_generate); ``generate_keys`` also evaluates every node's
+public key share and leaves them loaded as the new era's key set (NetworkInfo::new,
+src/messaging.rs:253-256) in the same call; ``public_key_shares`` is Commitment::evaluate(i + 1)
+for every node of a given commitment (hbtc_commitment_evaluate).
 Values on the wire use hbbft_amd/wire.py's bincode framing (parity-unpinned Fr layout).
 """
 import secrets
@@ -300,23 +302,35 @@ class SyncKeyGen:
     def is_ready(self):
         return self.count_complete() > self.t
 
-    def generate(self):
-        """(public key set commitment [t+1 compressed G1], our secret key share or None)."""
+    def _generate(self, n_nodes, load_keyset):
+        """One hbtc_skg_generate call over the complete Parts: (commit, sk, pk_shares, keyset id)."""
         t = self.t
         done = [self.parts[p] for p in sorted(self.parts) if self.parts[p].is_complete(t)]
-        if done:
-            pts = [st.commit[coeff_pos(0, j)] for j in range(t + 1) for st in done]
-            commit, st = self.ctx.g1_msm(t + 1, len(done), pts, [1] * len(pts))
-            if st.any():
-                raise N.HbtcError("generate: a commitment point failed to decode")
-        else:
-            commit = []  # Poly::zero().commitment(): no coefficients
-        sk = None
-        if self.our_idx is not None:
-            sk = 0
-            for st in done:  # Poly::interpolate(values.take(t + 1)).evaluate(0)
-                sk = (sk + _lagrange_at_zero(sorted(st.values.items())[:t + 1])) % R
+        if not done:
+            # Poly::zero().commitment(): no coefficients, so every share is the point at infinity
+            # and there is nothing to load
+            return [], (0 if self.our_idx is not None else None), [G1_INF] * n_nodes, None
+        row0 = [[st.commit[coeff_pos(0, j)] for j in range(t + 1)] for st in done]
+        values = None
+        if self.our_idx is not None:  # Poly::interpolate(values.take(t + 1)).evaluate(0)
+            values = [sorted(st.values.items())[:t + 1] for st in done]
+        commit, sk, pks, kid, status = self.ctx.skg_generate(t, row0, values, n_nodes, load_keyset)
+        if status == N.DECODE_ERR:
+            raise N.HbtcError("generate: a commitment point failed to decode")
+        if status != N.ACCEPT:
+            raise N.HbtcError("generate: %s" % N.STATUS_NAMES.get(status, status))
+        return commit, sk, pks, kid
+
+    def generate(self):
+        """(public key set commitment [t+1 compressed G1], our secret key share or None)."""
+        commit, sk, _, _ = self._generate(0, False)
         return commit, sk
+
+    def generate_keys(self):
+        """SyncKeyGen::generate followed by NetworkInfo::new in one device call: (commit, our secret
+        key share or None, every node's public key share, the id of the key set loaded from those
+        shares with commit[0] as its master key; None when no Part is complete)."""
+        return self._generate(len(self.ids), True)
 
     def public_key_shares(self, commit):
         """public_key_share(i) = commitment.evaluate(i + 1) for every node (messaging.rs:253-256)."""

@@ -27,6 +27,9 @@
  *   hbtc_encrypt             PublicKey::encrypt_with_rng (HoneyBadger::propose src/honey_badger/honey_badger.rs:98-114,
  *                            Part rows and Ack values src/sync_key_gen.rs:320-322,372-379)
  *   hbtc_fr_poly_eval        BivarPoly::row / Poly::evaluate over Fr (src/sync_key_gen.rs:320,374)
+ *   hbtc_skg_generate        SyncKeyGen::generate + NetworkInfo::new: the era's PublicKeySet, our secret key
+ *                            share and every public key share, loaded as a key set
+ *                                                                             src/sync_key_gen.rs:428-447, src/messaging.rs:253-256
  *   hbtc_g1_msm/hbtc_g2_msm  batched Pippenger MSMs (BivarCommitment::row / Commitment::evaluate,
  *                            src/sync_key_gen.rs:345,366,493); the combines run on the same kernels
  *
@@ -224,6 +227,39 @@ int hbtc_encrypt(hbtc_ctx* ctx, uint32_t n, const uint8_t* pk_c48, uint32_t pk_s
  * row(i + 1) (n_poly = 1 per Part, n_x = N; src/sync_key_gen.rs:372-379). */
 int hbtc_fr_poly_eval(hbtc_ctx* ctx, uint32_t n_poly, uint32_t n_coeff, const uint8_t* coeffs_le32,
                       uint32_t n_x, const uint8_t* x_le32, uint8_t* out_le32);
+
+/* SyncKeyGen::generate followed by NetworkInfo::new (src/sync_key_gen.rs:428-447,
+ * src/messaging.rs:253-256) in one call, device-resident between its stages (DESIGN.md "Key
+ * generation"): one upload of the inputs, one download of the outputs, one wait at the end.
+ * The n_parts >= 1 Parts are the complete ones in proposer order (the caller filters with
+ * is_complete).
+ *   row0_c48      [n_parts][t + 1] compressed G1: coefficient (0, j) of Part p's BivarCommitment
+ *   val_offsets   HOST, n_parts + 1 entries (CSR over the stored values of each Part), or NULL for
+ *                 an observer: no secret share is made and out_sk_le32 must be NULL too
+ *   val_x         x = sender index + 1 of every stored value, in the BTreeMap's order
+ *   vals_le32     the values, 32-byte little-endian, any value < 2^256, taken mod r
+ * Results:
+ *   out_commit_c48[j]    = sum_p row0[p][j]: the PublicKeySet's commitment, t + 1 points
+ *   out_pk_shares_c48[i] = sum_j (i + 1)^j out_commit[j] for i < n_nodes (may be NULL)
+ *   out_sk_le32          = sum_p L_p(0) mod r, canonical, with L_p the polynomial interpolated through
+ *                          Part p's values (Poly::interpolate: 0 to t + 1 of them, a Part without
+ *                          values contributes 0)
+ *   *out_keyset_id       (may be NULL) the n_nodes shares as a loaded key set with out_commit[0] as its
+ *                          master key: what hbtc_keyset_load(out_pk_shares) followed by
+ *                          hbtc_keyset_set_master(out_commit[0]) gives, built from the points already
+ *                          decoded on the device
+ * *status = HBTC_ACCEPT, HBTC_DECODE_ERR (a row0 point does not decode: the encodings hbtc_g1_msm
+ * rejects) or HBTC_DUPLICATE_ENTRY (an x repeats inside one Part).  On a status other than ACCEPT
+ * every output is zero-filled, no key set is created and *out_keyset_id is left untouched.  The
+ * point at infinity is a valid coefficient, and a sum that cancels gives the infinity encoding.
+ * HBTC_ERR_ARG: n_parts == 0, n_nodes == 0 with out_keyset_id, more than t + 1 values in a Part,
+ * x == 0, val_offsets and out_sk_le32 not both set or both NULL.  n_nodes == 0 is otherwise
+ * allowed (only the commitment and the secret share).  The device staging of the values and of the
+ * secret share is zeroed before the call returns. */
+int hbtc_skg_generate(hbtc_ctx* ctx, uint32_t n_parts, uint32_t t, const uint8_t* row0_c48,
+                      const uint32_t* val_offsets, const uint32_t* val_x, const uint8_t* vals_le32,
+                      uint32_t n_nodes, uint8_t* out_commit_c48, uint8_t* out_pk_shares_c48,
+                      uint8_t* out_sk_le32, uint32_t* out_keyset_id, int32_t* status);
 
 /* ---- host hashes (no context, no GPU) ----------------------------------------------------- */
 /* threshold_crypto's crate-internal hash_g2(msg) -> compressed G2 (96 B), and hash_g1_g2(g1, msg)
@@ -603,7 +639,9 @@ int hbtc_merkle_validate_dev(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const 
  * "mul", "rlc_items", "chk_tiles", "chk_tiles_w", "chk_halves", "chk_halves_w", "chk_subs",
  * "chk_subs_w", "chk_leaves", "rlc_finalize", "rs", "merkle",
  * "merkle_validate", "dec_pad" (k_dec_seed + k_enc_pad behind a combine or hbtc_decrypt's
- * multiplication).  Reading
+ * multiplication), "keygen" (hbtc_skg_generate, the whole call on the device) and its stages
+ * "keygen_sum" (row0 decode + column sums), "keygen_sk" (the interpolations), "keygen_shares"
+ * (commitment evaluation); its key-set tables count under "prepare".  Reading
  * synchronises the stream. */
 int hbtc_timing_enable(hbtc_ctx* ctx, int enable);
 int hbtc_timing_read(hbtc_ctx* ctx, const char* family, double* total_ms, uint64_t* launches);

@@ -13,6 +13,7 @@
 //!   ThresholdDecryption::try_output, to the plaintext     threshold_decrypt   (src/threshold_decryption.rs:164-188)
 //!   SyncKeyGen::handle_part / handle_ack                  skg_check_parts / skg_check_acks / decrypt
 //!   HoneyBadger::propose, SyncKeyGen::new / Ack values     encrypt / fr_poly_eval (src/sync_key_gen.rs:320-322,372-379)
+//!   SyncKeyGen::generate + NetworkInfo::new               skg_generate        (src/sync_key_gen.rs:428-447)
 #![allow(clippy::too_many_arguments)]
 pub mod ffi;
 #[cfg(feature = "experimental-queues")]
@@ -309,6 +310,57 @@ impl Context {
         })?;
         Ok(out)
     }
+
+    /// SyncKeyGen::generate + NetworkInfo::new in one call (written against the C ABI and, like the
+    /// rest of this crate, not compiled in this repository's checks).  `row0_c48`: coefficient
+    /// (0, j) of every complete Part's commitment, Part-major, t + 1 points each.  `values`: the
+    /// stored values as (CSR offsets over the Parts, x = sender index + 1, 32-byte LE values), or
+    /// None for an observer.  With `load_keyset` the n_nodes shares become a loaded key set whose
+    /// master key is the commitment's constant term.  On a status other than ACCEPT the outputs
+    /// are zero-filled and no key set exists.
+    pub fn skg_generate(&self, t: u32, row0_c48: &[u8], values: Option<(&[u32], &[u32], &[u8])>,
+                        n_nodes: u32, load_keyset: bool) -> Result<GeneratedKeys> {
+        let t1 = t as usize + 1;
+        assert!(!row0_c48.is_empty() && row0_c48.len() % (48 * t1) == 0, "t + 1 points per Part");
+        let n_parts = row0_c48.len() / (48 * t1);
+        if let Some((off, x, v)) = values {
+            assert_eq!(off.len(), n_parts + 1, "one offset per Part and the end");
+            assert!(off[0] == 0 && off.windows(2).all(|w| w[0] <= w[1]), "offsets start at 0 and do not decrease");
+            let n = off[n_parts] as usize;
+            assert!(x.len() == n && v.len() == 32 * n, "one x and one 32-byte value per stored value");
+        }
+        let mut commit = vec![0u8; 48 * t1];
+        let mut pk_shares = vec![0u8; 48 * n_nodes as usize];
+        let mut sk = [0u8; 32];
+        let (mut id, mut status) = (0u32, -1i32);
+        let (off_p, x_p, v_p, sk_p) = match values {
+            Some((off, x, v)) => (off.as_ptr(), x.as_ptr(), v.as_ptr(), sk.as_mut_ptr()),
+            None => (ptr::null(), ptr::null(), ptr::null(), ptr::null_mut()),
+        };
+        self.ok(unsafe {
+            ffi::hbtc_skg_generate(self.raw, n_parts as u32, t, row0_c48.as_ptr(), off_p, x_p, v_p, n_nodes,
+                                   commit.as_mut_ptr(),
+                                   if n_nodes > 0 { pk_shares.as_mut_ptr() } else { ptr::null_mut() }, sk_p,
+                                   if load_keyset { &mut id } else { ptr::null_mut() }, &mut status)
+        })?;
+        Ok(GeneratedKeys {
+            commit,
+            pk_shares,
+            sk: values.map(|_| sk),
+            keyset_id: if load_keyset && status == ACCEPT { Some(id) } else { None },
+            status,
+        })
+    }
+}
+
+/// What `Context::skg_generate` returns: the PublicKeySet's commitment (t + 1 compressed G1), every
+/// node's public key share, our secret key share (None for an observer), the loaded key set.
+pub struct GeneratedKeys {
+    pub commit: Vec<u8>,
+    pub pk_shares: Vec<u8>,
+    pub sk: Option<[u8; 32]>,
+    pub keyset_id: Option<u32>,
+    pub status: i32,
 }
 
 impl Drop for Context {
