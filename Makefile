@@ -14,7 +14,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/hbtc.h
 BUILD := build
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC)
 PARTS := 1
-RLC_PARTS := 6
+RLC_PARTS := 6 7
 MSM_PARTS := 8 9
 SKG_PARTS := 10
 KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_PARTS),$(BUILD)/hbtc_rlc.p$(p).o) \
@@ -50,6 +50,11 @@ $(BUILD)/hbtc_kernels.p%.o: $(CSRC)/hbtc_kernels.hip $(HDRS) | $(BUILD)
 # (isolated 48.5 vs 49.9 ms): the pass is VALU-issue-bound, not instruction-fetch-bound.
 $(BUILD)/hbtc_rlc.p6.o: $(CSRC)/hbtc_rlc.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=6 -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
+
+# part 7 (k_rlc_tree, the tile sums) in an object of its own, so its product form and occupancy
+# are chosen apart from the item kernels' (DESIGN.md §4 "The tile sums as a kernel of their own")
+$(BUILD)/hbtc_rlc.p7.o: $(CSRC)/hbtc_rlc.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=7 -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
 
 $(BUILD)/hbtc_rlc.p%.o: $(CSRC)/hbtc_rlc.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=$* -c $< -o $@
@@ -135,6 +140,12 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=$(PART) -c $(CSRC)/hbtc_kernels.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
 
+# the DecryptionShare item pass (k_rlc_decode, k_rlc_rpk, k_rlc_items, k_rlc_tree) with its own flags
+.PHONY: resources-rlc
+resources-rlc:
+	for p in 6 7; do $(HIPCC) $(HIPFLAGS) -DHBTC_PART=$$p -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE $(RLC_FLAGS) -c $(CSRC)/hbtc_rlc.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"; done
+
 .PHONY: resources-enc
 resources-enc:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
@@ -146,7 +157,17 @@ resources-keygen:
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
 
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
-          tests/native/libhbtc_keygen_hosttest.so
+          tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so
+# rlc_tree.h's host build (the body of k_rlc_tree replayed merge by merge, every output against a
+# plain restatement of the sums)
+tests/native/libhbtc_tree_hosttest.so: tests/native/hbtc_tree_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_tree_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-tree
+sanitize-tree: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_tree_host_main.cpp tests/native/hbtc_tree_hosttest.cpp -o $(BUILD)/tree_host_asan
+	$(BUILD)/tree_host_asan
 tests/native/libhbtc_keygen_hosttest.so: tests/native/hbtc_keygen_hosttest.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_keygen_hosttest.cpp -o $@
 # keygen.h's host build (the column sum, the interpolation at 0 over its 256 simulated lanes, the
@@ -181,8 +202,16 @@ $(BUILD)/hbtc_devtest.inl.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
 $(BUILD)/hbtc_devtest.call.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-devtest: tests/native/libhbtc_devtest.so
+devtest: tests/native/libhbtc_devtest.so tests/native/libhbtc_tree_devtest.so
 tests/native/libhbtc_devtest.so: $(DEVTEST_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
+# test-only device harness of the tile tree (tests/test_gpu_rlc_tree.py): rlc_reduce_sp on one wave
+# per tile beside the product's k_rlc_tree (the harness includes hbtc_rlc.hip), with the flags of
+# hbtc_rlc.p6.o; the object stays out of $(BUILD)/*.o, which tools/build_variant.sh links
+$(BUILD)/tree_devtest/hbtc_tree_devtest.o: tests/native/hbtc_tree_devtest.hip $(CSRC)/hbtc_rlc.hip $(HDRS) | $(BUILD)
+	mkdir -p $(BUILD)/tree_devtest
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
+tests/native/libhbtc_tree_devtest.so: $(BUILD)/tree_devtest/hbtc_tree_devtest.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 
 oracle: oracle/c/libtcoracle.so

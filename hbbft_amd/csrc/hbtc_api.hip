@@ -930,9 +930,17 @@ int rlc_dec_pass(hbtc_ctx* c, Keyset* ks, uint32_t n_ct, const uint32_t* offsets
   // pass has its own key and, under its workspace suffix, its own table
   G1J* rpk = nullptr;
   if (!exact) HB_TRY(wst(c, "rlc.rpk", ks->n, &rpk));
+  // the tile-sum tree's inputs and nodes (hbtc_rlc.hip k_rlc_tree): one mask per tile, and its P
+  // nodes (the S nodes live in t1s)
+  uint64_t* masks = nullptr;
+  G1J* pnodes = nullptr;
+  if (rlc_items_tree()) {
+    HB_TRY(wst(c, "rlc.masks", n_tiles, &masks));
+    if (!exact) HB_TRY(wst(c, "rlc.pnodes", rlc_tree_pnodes(n_tiles), &pnodes));
+  }
   HB_TRY(timed(c, "rlc_items", [&] {
     return launch_rlc_items(c->stream, n_tiles, tiles, d_idx, d_share, ks->pk, ks->st, ks->tab,
-                            ks->n, key, sus, sums, dec, d_status, t1s, rpk,
+                            ks->n, key, sus, sums, dec, d_status, t1s, rpk, masks, pnodes,
                             c->lanes[c->lane].dec_done);
   }));
   c->lanes[c->lane].dec_rec = rlc_items_split();

@@ -85,12 +85,20 @@ hipError_t launch_pk_table(hipStream_t s, const G1A* pk, const int32_t* pk_statu
 // split item pass (k_rlc_decode + k_rlc_items): t1s is n_items G1J of workspace ([|x|] d)
 // rpk: n_pk G1J of per-call workspace, the sender table R_id = [r_id] pk_id the launch fills
 // before the item pass reads it (the scalars are keyed by the sender; unused when sus.all)
+// tile sums by k_rlc_tree (rlc_tree.h; rlc_items_tree()): k_rlc_items leaves S_i in t1s and the
+// tile's ballot of summed lanes in masks (n_tiles words); pnodes is rlc_tree_pnodes(n_tiles) G1J
+// of workspace for the tree's P nodes.  Both unused (may be null) when built without the tree.
 bool rlc_items_split();
+bool rlc_items_tree();
+constexpr size_t rlc_tree_pnodes(size_t n_tiles) { return 32 * n_tiles; }
 hipError_t launch_rlc_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
                             const uint8_t* shares, const G1A* pk, const int32_t* pk_status,
                             const PtXY* pk_tab, uint32_t n_pk, RlcKey key, Suspects sus,
                             TileSums* sums, G1A* dec, int32_t* status, G1J* t1s, G1J* rpk,
-                            hipEvent_t after_decode = nullptr);
+                            uint64_t* masks, G1J* pnodes, hipEvent_t after_decode = nullptr);
+// the tree alone (launch_rlc_items ends with it; built apart from the item kernels, Makefile)
+hipError_t launch_rlc_tree(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
+                           const uint64_t* masks, G1J* t1s, G1J* pnodes, const G1J* rpk, TileSums* sums);
 // Final decisions; with last_bad != null, counts every sender's REJECTs in `rejects` and stamps
 // last_bad[i] = now for the senders with >= thresh of them (clearing the counts).
 hipError_t launch_status_remap(hipStream_t s, uint32_t n, int32_t* status, int32_t from, int32_t to);

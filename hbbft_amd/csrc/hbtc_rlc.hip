@@ -32,7 +32,9 @@
 // == 1 with a nonzero exponent on a wrong share, i.e. with probability <= 2^-k per p (the same
 // argument as the plain check), <= |G| 2^-k per located group; such groups are split.
 //
-// This file holds the per-item pass (k_rlc_items: decode, r_i, the tile and sub-tile sums)
+// This file holds the per-item pass (k_rlc_decode: decode; k_rlc_items: r_i d_i, left in the
+// share's workspace slot with the tile's mask of summed lanes; k_rlc_tree: the tile and sub-tile
+// sums of 8 tiles per workgroup, every level's merges dense over the threads, rlc_tree.h)
 // and the final decision (k_rlc_finalize); the pairing-product checks of those sums run on
 // the cooperative GT arithmetic in hbtc_check.hip:
 //     k_chk_plain / k_chk_pair   plain (and weighted) checks of every 64-share tile; a failing
@@ -41,14 +43,37 @@
 //                   child derived), single wrong shares located at every level
 //     k_chk_leaves  the exact per-share check for eighths with >= 2 wrong shares
 // Work per share in the honest case: decode + r_i d_i (the x-adic joint double-and-add, curve.h
-// xadic_mul_uniform) + a load of r_i pk_i from the call's sender table + a share of the wave's
+// xadic_mul_uniform) + a load of r_i pk_i from the call's sender table + a share of the tile's
 // reduction tree; the pairing work is per group.
 #include "rlc_common.h"
+#include "rlc_tree.h"
 
 #ifndef HBTC_PART
 #define HBTC_PART 0
 #endif
 #define HBTC_IN_PART(n) (HBTC_PART == 0 || HBTC_PART == (n))
+
+// The item pass as two kernels: the decode half at three waves per SIMD (332 B/lane), the scalar
+// half at two (its x-adic table) -- C3 13.6 -> 14.1 M shares/s against the single two-wave kernel
+// (profiles/r05/run12/)
+#ifndef HBTC_RLC_SPLIT
+#define HBTC_RLC_SPLIT 1
+#endif
+// The tile sums in a kernel of their own (k_rlc_tree, rlc_tree.h) instead of a tree on every
+// tile's wave at the end of k_rlc_items (rlc_common.h rlc_reduce_sp; HBTC_RLC_TREE=0 builds that
+// form for comparisons).  Needs the split pass: S_i takes the share's [|x|] d slot.
+#ifndef HBTC_RLC_TREE
+#define HBTC_RLC_TREE 1
+#endif
+#if HBTC_RLC_TREE && !HBTC_RLC_SPLIT
+#error "HBTC_RLC_TREE needs HBTC_RLC_SPLIT (S_i is left in the t1 workspace)"
+#endif
+#ifndef HBTC_TREE_WAVES
+#define HBTC_TREE_WAVES 2  // minimum waves per SIMD of k_rlc_tree's register allocation
+#endif
+#ifndef HBTC_TREE_PRIO
+#define HBTC_TREE_PRIO 0  // wave priority of k_rlc_tree (experiments)
+#endif
 
 namespace hbtc {
 
@@ -58,7 +83,9 @@ namespace hbtc {
 // sender's x-adic scalar r_i = d0 + d1 x + d2 mu + d3 mu x (four ChaCha20 digits of key.bits / 4
 // bits, mu = -x^2 the eigenvalue of phi: 2^key.bits distinct residues mod r, rlc_common.h),
 // compute r_i d_i by one joint double-and-add over the digits' bits (curve.h xadic_mul_uniform),
-// load r_i pk_i from the call's sender table, then the plain and weighted group sums.  Items
+// and hand r_i d_i and the tile's mask of summed lanes to k_rlc_tree, which loads r_i pk_i from
+// the call's sender table and forms the plain and weighted group sums (HBTC_RLC_TREE=0: both
+// here, on the tile's own wave).  Items
 // that cannot be checked (decode error, unknown sender) get their final status
 // here and contribute the identity; a ciphertext whose own H / w failed to decode is resolved
 // by k_rlc_finalize.  Needs nothing from the per-ciphertext preparation, so it runs
@@ -74,12 +101,6 @@ namespace hbtc {
 // the whole 8-entry table in registers + AGPRs 11.7 M, two waves with the table partly spilled
 // 13.4 M, profiles/r05/run1/)
 #define HBTC_ITEMS_WAVES 2
-#endif
-// The item pass as two kernels: the decode half at three waves per SIMD (332 B/lane), the scalar
-// half at two (its x-adic table) -- C3 13.6 -> 14.1 M shares/s against the single two-wave kernel
-// (profiles/r05/run12/)
-#ifndef HBTC_RLC_SPLIT
-#define HBTC_RLC_SPLIT 1
 #endif
 #ifndef HBTC_RLC_DEC_WAVES
 #define HBTC_RLC_DEC_WAVES 3
@@ -150,22 +171,24 @@ __global__ void __launch_bounds__(64, HBTC_ITEMS_WAVES) k_rlc_items(
     const Tile* __restrict__ tiles, const uint32_t* __restrict__ idx,
     const uint8_t* __restrict__ shares, const int32_t* __restrict__ pk_status, uint32_t n_pk,
     RlcKey key, Suspects sus, TileSums* __restrict__ sums, G1A* __restrict__ dec,
-    int32_t* __restrict__ status, const G1J* __restrict__ t1s, const G1J* __restrict__ rpk) {
+    int32_t* __restrict__ status, G1J* __restrict__ t1s, const G1J* __restrict__ rpk,
+    uint64_t* __restrict__ masks) {
 #if HBTC_ITEMS_PRIO > 0
   __builtin_amdgcn_s_setprio(HBTC_ITEMS_PRIO);
 #endif
-  // the reduction's two arrays, and before them the x-adic table's three LDS entries (18 KB:
-  // 3 x 24 words x 64 lanes, curve.h xadic_mul_sac8<LDS3>): one wave per block, so the table
-  // reads are over before the reduction writes
+  // the x-adic table's three LDS entries (18 KB: 3 x 24 words x 64 lanes, curve.h
+  // xadic_mul_sac8<LDS3>); with HBTC_RLC_TREE=0 also the reduction's two arrays after them: one
+  // wave per block, so the table reads are over before the reduction writes
   __shared__ G1J red[128];
-  G1J* redA = red;
-  G1J* redB = red + 64;
   const Tile tile = tiles[blockIdx.x];
   const uint32_t lane = threadIdx.x;
   const size_t item = (size_t)tile.first + lane;
-  G1J S, P;
+  G1J S;
   jac_set_inf(S);
+#if !HBTC_RLC_TREE
+  G1J P;
   jac_set_inf(P);
+#endif
   int32_t st = HBTC_RLC_PENDING;
   uint32_t id = 0;
   bool sum = false;  // this share enters the group sums
@@ -240,12 +263,25 @@ __global__ void __launch_bounds__(64, HBTC_ITEMS_WAVES) k_rlc_items(
       xadic_mul_uniform(S, d, xp, pxp, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits);
 #endif
     }
+#if !HBTC_RLC_TREE
     P = rpk[id];  // [r_id] pk_id, the identity for a key at infinity
+#endif
   }
+#if HBTC_RLC_TREE
+  // S_i (the identity for a lane outside the sums) over the share's own [|x|] d slot, which is
+  // dead now, and the tile's mask: k_rlc_tree forms the sums
+  if (lane < tile.count) t1s[item] = S;
+  const uint64_t m = __ballot(sum);
+  if (lane == 0) masks[blockIdx.x] = m;
+#else
+  G1J* redA = red;
+  G1J* redB = red + 64;
   TileSums* ts = sums + blockIdx.x;
   rlc_reduce_sp(redA, redB, S, P, lane, ts->S, ts->SW, ts->P, ts->PW, ts->SH, ts->SHW, ts->PH,
                 ts->PHW, ts->SQ, ts->SQW, ts->PQ, ts->PQW);
+#endif
 }
+
 #endif  // part 6
 
 #if HBTC_IN_PART(6)
@@ -297,16 +333,65 @@ __global__ void __launch_bounds__(256) k_track_update(uint32_t n_pk, uint32_t* _
 }
 #endif  // part 6
 
+#if HBTC_IN_PART(7) && HBTC_RLC_TREE
+// The tile sums of TREE_G consecutive tiles per workgroup (rlc_tree.h): at every level the
+// merges of all the group's tiles, both sides, densely over the threads; the nodes go through
+// global memory (the S_i slots and pnodes) between barriers.  A thread's merges of one level
+// are TREE_BS apart, so whole waves run out of work together and skip the level.  Two waves per
+// workgroup: a wave that waits at a barrier holds its registers, and with four waves (16 tiles)
+// the waiting ones kept the other lanes' kernels off the SIMDs -- the whole gain.
+static_assert(sizeof(TileSums) == TS_G1J * sizeof(G1J) && offsetof(TileSums, P) == TS_P * sizeof(G1J) &&
+                  offsetof(TileSums, SW) == TS_SW * sizeof(G1J) && offsetof(TileSums, PW) == TS_PW * sizeof(G1J) &&
+                  offsetof(TileSums, SH) == TS_SH * sizeof(G1J) && offsetof(TileSums, SHW) == TS_SHW * sizeof(G1J) &&
+                  offsetof(TileSums, PH) == TS_PH * sizeof(G1J) && offsetof(TileSums, PHW) == TS_PHW * sizeof(G1J) &&
+                  offsetof(TileSums, SQ) == TS_SQ * sizeof(G1J) && offsetof(TileSums, SQW) == TS_SQW * sizeof(G1J) &&
+                  offsetof(TileSums, PQ) == TS_PQ * sizeof(G1J) && offsetof(TileSums, PQW) == TS_PQW * sizeof(G1J),
+              "rlc_tree.h addresses TileSums as an array of G1J");
+__global__ void __launch_bounds__(TREE_BS, HBTC_TREE_WAVES) k_rlc_tree(
+    uint32_t n_tiles, const Tile* __restrict__ tiles, const uint32_t* __restrict__ idx,
+    const uint64_t* __restrict__ masks, G1J* t1s, G1J* pnodes, const G1J* __restrict__ rpk,
+    TileSums* sums) {
+#if HBTC_TREE_PRIO > 0
+  __builtin_amdgcn_s_setprio(HBTC_TREE_PRIO);
+#endif
+  __shared__ TreeTile tt[TREE_G];
+  const uint32_t t0 = blockIdx.x * TREE_G;
+  const uint32_t g_tiles = n_tiles - t0 < TREE_G ? n_tiles - t0 : TREE_G;
+  for (uint32_t t = threadIdx.x; t < g_tiles; t += TREE_BS) {
+    const Tile tile = tiles[t0 + t];
+    tt[t] = TreeTile{tile.first, tile.count, masks[t0 + t]};
+  }
+  __syncthreads();
+  G1J* const pn = pnodes + (size_t)t0 * TREE_P_SLOTS;
+  G1J* const out = reinterpret_cast<G1J*>(sums + t0);
+#pragma unroll 1
+  for (uint32_t level = 1; level <= TREE_LEVELS; ++level) {
+    const uint32_t n = tree_level_merges(TREE_G, level);
+#pragma unroll 1
+    for (uint32_t u = threadIdx.x; u < n; u += TREE_BS) tree_merge(level, u, g_tiles, tt, t1s, pn, rpk, idx, out);
+    __syncthreads();  // the next level reads these nodes (global memory, workgroup scope)
+  }
+}
+hipError_t launch_rlc_tree(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
+                           const uint64_t* masks, G1J* t1s, G1J* pnodes, const G1J* rpk, TileSums* sums) {
+  if (n_tiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rlc_tree, dim3((n_tiles + TREE_G - 1) / TREE_G), dim3(TREE_BS), 0, s, n_tiles, tiles,
+                     idx, masks, t1s, pnodes, rpk, sums);
+  return hipGetLastError();
+}
+#endif  // part 7
+
 // ------------------------------------------------------------------------------ launchers
 static inline uint32_t rlc_blocks(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 
 #if HBTC_IN_PART(6)
 bool rlc_items_split() { return HBTC_RLC_SPLIT != 0; }
+bool rlc_items_tree() { return HBTC_RLC_TREE != 0; }
 hipError_t launch_rlc_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
                             const uint8_t* shares, const G1A* pk, const int32_t* pk_status,
                             const PtXY* pk_tab, uint32_t n_pk, RlcKey key, Suspects sus,
                             TileSums* sums, G1A* dec, int32_t* status, G1J* t1s, G1J* rpk,
-                            hipEvent_t after_decode) {
+                            uint64_t* masks, G1J* pnodes, hipEvent_t after_decode) {
   if (n_tiles == 0) return hipSuccess;
   hipError_t e;
   // the sender table: not in the exact mode, where no share enters the sums
@@ -322,7 +407,14 @@ hipError_t launch_rlc_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, 
   if (after_decode && (e = hipEventRecord(after_decode, s)) != hipSuccess) return e;
 #endif
   hipLaunchKernelGGL(k_rlc_items, dim3(n_tiles), dim3(64), 0, s, tiles, idx, shares, pk_status, n_pk,
-                     key, sus, sums, dec, status, t1s, rpk);
+                     key, sus, sums, dec, status, t1s, rpk, masks);
+#if HBTC_RLC_TREE
+  // the tile sums: not in the exact mode, where no share enters them and no check reads them
+  if (!sus.all) {
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return launch_rlc_tree(s, n_tiles, tiles, idx, masks, t1s, pnodes, rpk, sums);
+  }
+#endif
   return hipGetLastError();
 }
 hipError_t launch_rlc_finalize(hipStream_t s, uint32_t n_tiles, const Tile* tiles,

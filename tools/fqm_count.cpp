@@ -118,7 +118,10 @@ int main() {
   // correction, computed by every lane) over nbits = 16 (64-bit RLC)
   // or 32 (128-bit) digit bits, and the item's share of the plain + position-weighted reduction
   // tree of its tile: per side 3 * 63 Jacobian additions and 57 doublings, two sides, over 64
-  // items.  r*pk costs the item nothing: the scalar is keyed by the sender and [r_id] pk_id comes
+  // items (the merges are the same whether the tile's own wave forms them, rlc_reduce_sp, or
+  // k_rlc_tree lists them densely over a workgroup, rlc_tree.h: only the idle lanes' issue
+  // slots differ, which this count never held).
+  // r*pk costs the item nothing: the scalar is keyed by the sender and [r_id] pk_id comes
   // from the call's sender table (n_pk fixed-base multiplications per call, not counted here)
   const uint32_t dg[4] = {0xa5a55a5au, 0x5a5aa5a5u, 0x3c3cc3c3u, 0xc3c33c3cu};
   G1J rd;  // a generic accumulator, for the tree costs below
