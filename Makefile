@@ -20,7 +20,7 @@ SKG_PARTS := 10
 KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_PARTS),$(BUILD)/hbtc_rlc.p$(p).o) \
          $(foreach p,$(MSM_PARTS),$(BUILD)/hbtc_msm.p$(p).o) $(foreach p,$(SKG_PARTS),$(BUILD)/hbtc_skg.p$(p).o) \
          $(BUILD)/hbtc_check.c1.o $(BUILD)/hbtc_check.c2.o $(BUILD)/hbtc_sig.s1.o $(BUILD)/hbtc_sig.s2.o $(BUILD)/hbtc_pb.o \
-         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o
+         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o $(BUILD)/hbtc_own.o
 LIB := hbbft_amd/libhbtc.so
 
 .PHONY: all lib hosttest devtest oracle clean resources roofline-constants
@@ -117,6 +117,11 @@ $(BUILD)/hbtc_enc.o: $(CSRC)/hbtc_enc.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_keygen.o: $(CSRC)/hbtc_keygen.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
 
+# SecretKeyShare::sign (k_sig_share: cofactor clearing and the GLV multiplication by one secret
+# scalar on lane pairs): the flag set of hbtc_enc.o (`make resources-own` prints the resource report)
+$(BUILD)/hbtc_own.o: $(CSRC)/hbtc_own.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
+
 # Reliable Broadcast: Reed-Solomon over GF(2^8), SHA3 Merkle trees and proofs
 $(BUILD)/hbtc_bcast.o: $(CSRC)/hbtc_bcast.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -156,8 +161,24 @@ resources-keygen:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_keygen.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
 
+.PHONY: resources-own
+resources-own:
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_own.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
+
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
-          tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so
+          tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
+          tests/native/libhbtc_own_hosttest.so
+# own_host.h's host build (the secret scalar of hbtc_decrypt_shares / hbtc_sign_shares: reduction,
+# the x^2 split, the base-|x| digits, the wiping)
+tests/native/libhbtc_own_hosttest.so: tests/native/hbtc_own_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_own_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-own
+sanitize-own: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_own_host_main.cpp tests/native/hbtc_own_hosttest.cpp -o $(BUILD)/own_host_asan
+	$(BUILD)/own_host_asan
 # rlc_tree.h's host build (the body of k_rlc_tree replayed merge by merge, every output against a
 # plain restatement of the sums)
 tests/native/libhbtc_tree_hosttest.so: tests/native/hbtc_tree_hosttest.cpp $(HDRS)

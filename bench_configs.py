@@ -48,6 +48,15 @@ checked against the construction after timing:
       calls: verify_dec_shares + combine_dec over the verified shares + xor_hash_bytes_batch on
       the host's cores, (c) the xor_hash_bytes_batch step of (b) alone.  (a) and (b) must give
       bit-equal plaintexts.  Reports median / minimum per path and the dec_pad kernel span.
+  own This node's own shares of an epoch (not in the default list), at n = 1000 and n = 10, host
+      buffers and the Python marshalling inside the timed region, the compared paths interleaved
+      in every repeat, outputs asserted bit-equal before timing: (dec) hbtc_decrypt_shares on n
+      ciphertexts of --td-bytes each (SecretKeyShare::decrypt_share, src/threshold_decryption.rs:98)
+      against the composition it replaces, hash_g1_g2_batch + verify_ciphertexts + g1_mul; (sig)
+      hbtc_sign_shares on n coin nonces (SecretKeyShare::sign, src/coin.rs:142) against
+      hash_g2_batch + g2_mul.  Reports median / minimum per path, the HIP-event spans of
+      "own_dec" / "own_sig" and their stages, and the ratio to the CPU baseline's 2,593 pair
+      checks/s as context.
 
   bc  Reliable Broadcast of one HoneyBadger epoch at N = 256 (the largest network hbbft's
       reed-solomon-erasure coding accepts: k + p <= 256), one node's view: the N^2 = 65,536 Echo
@@ -58,7 +67,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -88,7 +97,7 @@ G2_GEN = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bb
                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
 SEED = 0x6862626674
 N_OUT = 6  # output sets rotated per step (bench.py's N_OUT)
-STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5, "kg": 3}
+STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5, "kg": 3, "own": 7}
 
 
 def log(*a):
@@ -983,6 +992,118 @@ def bench_threshold_decrypt(ctx, n, v_bytes, steps, warmup, corrupt):
     }
 
 
+def bench_own_shares(ctx, v_bytes, steps, warmup):
+    """own: hbtc_decrypt_shares / hbtc_sign_shares against the calls they replace (see the docstring)."""
+    rng = random.Random(SEED + 99)
+    nrng = np.random.default_rng(SEED + 99)
+    sk = rng.randrange(1, R)
+    pk, st = ctx.g1_mul(G1_GEN, fr_bytes([sk]))
+    assert not st.any()
+    steps = max(steps, 7)
+    families = ("own_dec", "own_sig", "hash", "pb_items", "pb_lines", "pb_ml", "pb_checks", "pb_decode",
+                "sig_items", "chk_leaves", "rlc_finalize", "mul")
+
+    def stat(xs):
+        return {"median_ms": round(float(np.median(xs)), 3), "min_ms": round(min(xs), 3),
+                "max_ms": round(max(xs), 3)}
+
+    def spans(fn):
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        fn()
+        out = {}
+        for fam in families:
+            ms, launches = ctx.timing_read(fam)
+            if launches:
+                out[fam] = {"ms": round(ms, 3), "launches": int(launches)}
+        ctx.timing_enable(False)
+        return out
+
+    def compare(paths):
+        for _ in range(warmup):
+            for _, fn in paths:
+                fn()
+        times = {name: [] for name, _ in paths}
+        for _ in range(steps):  # interleaved: every repeat runs the paths back to back
+            for name, fn in paths:
+                t0 = time.perf_counter()
+                fn()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        return {name: stat(ts) for name, ts in times.items()}
+
+    out = {}
+    for n in (1000, 10):
+        msgs = [nrng.integers(0, 256, v_bytes, dtype=np.uint8).tobytes() for _ in range(n)]
+        cts, st = ctx.encrypt(bytes(pk), fr_bytes([rng.randrange(1, R) for _ in range(n)]), msgs)
+        assert not st.any()
+        us, vs, ws = [c[0] for c in cts], [c[1] for c in cts], [c[2] for c in cts]
+        ws[n // 2] = ws[0]  # one invalid ciphertext
+        last = {}
+
+        def dec_new():
+            last["new"] = ctx.decrypt_shares(sk, us, vs, ws)
+
+        def dec_composed():
+            H = ctx.hash_g1_g2_batch(us, vs)
+            vst = ctx.verify_ciphertexts(us, H, ws)
+            g, _ = ctx.g1_mul(us, ksame)
+            gb = g.tobytes()
+            last["old"] = ([gb[48 * i:48 * i + 48] if vst[i] == N.ACCEPT else None for i in range(n)], H, vst)
+
+        ksame = np.tile(fr_bytes([sk]), n)
+        dec_new()
+        dec_composed()
+        if last["new"][0] != last["old"][0] or last["new"][1] != last["old"][1] or \
+                list(last["new"][2]) != list(last["old"][2]):
+            raise SystemExit("own: hbtc_decrypt_shares differs from the composed path at n = %d" % n)
+        if sum(1 for x in last["new"][0] if x is None) != 1:
+            raise SystemExit("own: expected exactly one rejected ciphertext")
+        r = compare([("decrypt_shares", dec_new), ("composed", dec_composed)])
+        r["spans"] = spans(dec_new)
+        r["outputs_bit_equal"] = True
+        out["dec_n%d" % n] = r
+
+        nonces = [b"Nonce for Honey Badger " + repr([int(x) for x in nrng.integers(0, 256, 48)]).encode()
+                  + b"@%d:%d:%d" % (7, i, i % 3) for i in range(n)]
+
+        def sig_new():
+            last["snew"] = ctx.sign_shares(sk, nonces)
+
+        def sig_composed():
+            H = ctx.hash_g2_batch(nonces)
+            s, _ = ctx.g2_mul(H, ksame)
+            sb = s.tobytes()
+            last["sold"] = ([sb[96 * i:96 * i + 96] for i in range(n)], H)
+
+        sig_new()
+        sig_composed()
+        if last["snew"] != last["sold"]:
+            raise SystemExit("own: hbtc_sign_shares differs from the composed path at n = %d" % n)
+        r = compare([("sign_shares", sig_new), ("composed", sig_composed)])
+        r["spans"] = spans(sig_new)
+        r["outputs_bit_equal"] = True
+        r["nonce_bytes"] = len(nonces[0])
+        out["sig_n%d" % n] = r
+    d = out["dec_n1000"]
+    res = {
+        "metric": "own shares: ms per call, hbtc_decrypt_shares at n = 1000",
+        "value": d["decrypt_shares"]["median_ms"],
+        "unit": "ms per call (median of %d interleaved repeats)" % steps,
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "higher_is_better": False,
+        "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (one key, random ciphertexts of %d bytes with one invalid, coin-shaped "
+                "nonces); host buffers (PCIe-inclusive), Python marshalling included" % v_bytes,
+        "config": {"workload": "own: decrypt_share and sign at n = 1000 and n = 10", "v_bytes": v_bytes,
+                   "mode": "rlc" if ctx_mode[0] == N.MODE_RLC else "per_share", "sig_form": "psi split"},
+        # context only: the C restatement's two-pairing share check on 16 cores (README)
+        "cpu_pair_checks_per_s": 2593,
+        "decrypt_shares_per_s_n1000": round(1000 / (d["decrypt_shares"]["min_ms"] * 1e-3)),
+        "ratio_to_cpu_pair_checks": round(1000 / (d["decrypt_shares"]["min_ms"] * 1e-3) / 2593, 1),
+    }
+    res.update(out)
+    return res
+
+
 def bench_broadcast(ctx, n, value_bytes, steps, warmup):
     """bc: one node's Reliable Broadcast work for an epoch of n proposers (see the docstring)."""
     from hbbft_amd import broadcast as G
@@ -1127,7 +1248,7 @@ def main():
                     help="kg: also time, once, the calls generate_keys() replaced (Python interpolation "
                          "on 32 Parts, scaled)")
     ap.add_argument("--distinct", type=int, default=4, help="c5 distinct bivariate polynomials")
-    ap.add_argument("--td-bytes", type=int, default=1024, help="td: bytes per contribution")
+    ap.add_argument("--td-bytes", type=int, default=1024, help="td / own: bytes per contribution")
     ap.add_argument("--bc-value", type=int, default=65536, help="bc: bytes per proposed value")
     ap.add_argument("--mode", choices=["rlc", "per_share"], default="rlc")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
@@ -1159,6 +1280,8 @@ def main():
                 out = bench_broadcast(ctx, 256, args.bc_value, steps, warmup)
             elif c == "td":
                 out = bench_threshold_decrypt(ctx, args.nodes, args.td_bytes, steps, warmup, args.corrupt)
+            elif c == "own":
+                out = bench_own_shares(ctx, args.td_bytes, steps, warmup)
             elif c == "kg":
                 out = bench_keygen(ctx, args.nodes, steps, warmup, parent=args.kg_parent)
             elif c == "c5p":

@@ -119,6 +119,8 @@ SIGNATURES = {
     "hbtc_commitment_evaluate": (_I32, [_P, _U32, _P, _U32, _P, _P, _P]),
     "hbtc_decrypt": (_I32, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "hbtc_encrypt": (_I32, [_P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hbtc_decrypt_shares": (_I32, [_P, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hbtc_sign_shares": (_I32, [_P, _U32, _P, _P, _P, _P, _P]),
     "hbtc_fr_poly_eval": (_I32, [_P, _U32, _U32, _P, _U32, _P, _P]),
     "hbtc_skg_generate": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "hbtc_unframe_points_dev": (_I32, [_P, _U32, _U32, _P, _P]),
@@ -791,6 +793,51 @@ class Context:
         ub, vb, wb = u.tobytes(), v.tobytes(), w.tobytes()
         return [(ub[48 * i:48 * i + 48], vb[off[i]:off[i + 1]], wb[96 * i:96 * i + 96])
                 for i in range(n)], st
+
+    # ---- this node's own shares
+    def decrypt_shares(self, sk, us, vs, ws):
+        """SecretKeyShare::decrypt_share of the ciphertexts (u_i, v_i, w_i) under the secret key
+        share sk (an int below 2^256): ([share or None], [H], status).  H_i = hash_g1_g2(u_i, v_i)
+        for every item; share_i (48 bytes) where status is ACCEPT, else None."""
+        buf, off = _msg_batch(vs)
+        n = off.size - 1
+        if n == 0:
+            return [], [], np.zeros(0, np.int32)
+        u, w = _join(us, 48), _join(ws, 96)
+        if u.size != 48 * n or w.size != 96 * n:
+            raise ValueError("one 48-byte u and one 96-byte w per v")
+        g, H = np.zeros(48 * n, np.uint8), np.zeros(96 * n, np.uint8)
+        st = np.zeros(n, np.int32)
+        k = np.frombuffer(int(sk).to_bytes(32, "little"), np.uint8).copy()
+        try:
+            self._check(self.lib.hbtc_decrypt_shares(self.h, n, _ptr(k), _ptr(u), _ptr(buf), _ptr(off),
+                                                     _ptr(w), _ptr(g), _ptr(H), _ptr(st)),
+                        "hbtc_decrypt_shares")
+        finally:
+            k[:] = 0
+        gb, hb = g.tobytes(), H.tobytes()
+        return ([gb[48 * i:48 * i + 48] if st[i] == ACCEPT else None for i in range(n)],
+                [hb[96 * i:96 * i + 96] for i in range(n)], st)
+
+    def sign_shares(self, sk, msgs, want_H=True):
+        """SecretKeyShare::sign of every message under the secret key (share) sk: ([sig], [H])
+        with H_i = hash_g2(msg_i) and sig_i = sk H_i, 96 bytes each (H is None with want_H=False)."""
+        buf, off = _msg_batch(msgs)
+        n = off.size - 1
+        if n == 0:
+            return [], ([] if want_H else None)
+        sig = np.zeros(96 * n, np.uint8)
+        H = np.zeros(96 * n, np.uint8) if want_H else None
+        k = np.frombuffer(int(sk).to_bytes(32, "little"), np.uint8).copy()
+        try:
+            self._check(self.lib.hbtc_sign_shares(self.h, n, _ptr(k), _ptr(buf), _ptr(off), _ptr(sig),
+                                                  _ptr(H)), "hbtc_sign_shares")
+        finally:
+            k[:] = 0
+        sb = sig.tobytes()
+        hb = H.tobytes() if want_H else None
+        return ([sb[96 * i:96 * i + 96] for i in range(n)],
+                [hb[96 * i:96 * i + 96] for i in range(n)] if want_H else None)
 
     # ---- Fr polynomials
     def fr_poly_eval(self, coeffs, xs):

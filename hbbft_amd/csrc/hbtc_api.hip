@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "hbtc_kernels.h"
+#include "own_host.h"
 
 using namespace hbtc;
 
@@ -2741,30 +2742,6 @@ int hbtc_combine_sigs_verified_dev(hbtc_ctx* c, uint32_t n_inst, const uint32_t*
 }
 
 namespace {
-// k mod r for a 256-bit little-endian scalar (k < 2^256 < 3r: at most two subtractions)
-void scalar_mod_r(uint32_t* out, const uint8_t* in) {
-  static const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                                0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-  uint32_t k[8];
-  memcpy(k, in, 32);
-  for (int rep = 0; rep < 2; ++rep) {
-    bool ge = true;
-    for (int i = 7; i >= 0; --i)
-      if (k[i] != R[i]) {
-        ge = k[i] > R[i];
-        break;
-      }
-    if (!ge) break;
-    uint64_t borrow = 0;
-    for (int i = 0; i < 8; ++i) {
-      const uint64_t d = (uint64_t)k[i] - R[i] - borrow;
-      k[i] = (uint32_t)d;
-      borrow = (d >> 63) & 1u;
-    }
-  }
-  memcpy(out, k, 32);
-}
-
 // n_msm MSMs of n terms on s_comb from device buffers: term i of MSM m is compressed item
 // m * stride + i (terms i >= stride: the generator), canonical scalars [m][n].  Writes the
 // compressed results and ACCEPT / DECODE_ERR per MSM.
@@ -3338,38 +3315,109 @@ int hbtc_hash_g1_g2_batch_gpu(hbtc_ctx* c, uint32_t n, const uint8_t* g1_c48, co
   return hash_batch_gpu(c, n, g1_c48, msgs, offsets, out_c96);
 }
 
-// k (canonical, < r, 8 little-endian limbs) = k1 x^2 + k0 with k0 < x^2 and k1 < 2^128 (k < r <
-// x^4): binary long division by x^2 = 0xac45a4010001a4020000000100000000.
-static void split_by_x2(const uint32_t* k, uint32_t* k0, uint32_t* k1) {
-  static const uint32_t X2[4] = {0x00000000u, 0x00000001u, 0x0001a402u, 0xac45a401u};
-  uint32_t rem[5] = {0, 0, 0, 0, 0};
-  uint32_t q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int bit = 255; bit >= 0; --bit) {
-    for (int j = 4; j > 0; --j) rem[j] = (rem[j] << 1) | (rem[j - 1] >> 31);  // rem = 2 rem + bit
-    rem[0] = (rem[0] << 1) | ((k[bit >> 5] >> (bit & 31)) & 1u);
-    bool ge = rem[4] != 0;
-    if (!ge) {
-      ge = true;
-      for (int j = 3; j >= 0; --j)
-        if (rem[j] != X2[j]) {
-          ge = rem[j] > X2[j];
-          break;
-        }
-    }
-    if (ge) {
-      uint64_t borrow = 0;
-      for (int j = 0; j < 5; ++j) {
-        const uint64_t d = (uint64_t)rem[j] - (j < 4 ? X2[j] : 0u) - borrow;
-        rem[j] = (uint32_t)d;
-        borrow = (d >> 63) & 1u;
-      }
-      q[bit >> 5] |= 1u << (bit & 31);
-    }
+// the hash batches' message buffer; a batch of empty messages may come without one
+static int upload_msgs(hbtc_ctx* c, const uint8_t* msgs, size_t total, void** out) {
+  if (total == 0) return ws(c, "hash.msgs", 1, out);
+  return upload(c, "hash.msgs", msgs, total, out);
+}
+
+// A whole-call timing span whose events are released when the call fails before span_end
+// hands them to the context.
+struct SpanGuard {
+  Span sp{std::string(), nullptr, nullptr};
+  bool handed = false;
+  ~SpanGuard() {
+    if (handed) return;
+    if (sp.a) (void)hipEventDestroy(sp.a);
+    if (sp.b) (void)hipEventDestroy(sp.b);
   }
-  for (int j = 0; j < 4; ++j) {
-    k0[j] = rem[j];
-    k1[j] = q[j];
+};
+
+// SecretKey(Share)::decrypt_share's stages on the device, shared by hbtc_decrypt and
+// hbtc_decrypt_shares:
+//   1. H_i = hash_g1_g2(u_i, v_i); H and the uploaded v stay on the device.  defer_redraw false:
+//      the blocking hash batch (it waits to read its redraw flags and patches H itself).  True:
+//      the same two launches enqueued without a wait, u uploaded once for the hash and the pair
+//      check, and the flags ([h2] cand = O: the item's H is not valid) left in d_hst for the
+//      caller to read after its own final wait;
+//   2. Ciphertext::verify, e(G1, w) == e(u, H), under the context's verify mode -> d_st;
+//   3. g = sk u (compressed, d_g).  RLC mode: on the u the pair batch decoded, for the ACCEPTed
+//      items, zero bytes for the others (d_gst = null).  Per-share mode: every item from its
+//      bytes, the multiplication's own status in d_gst.
+// Nothing is downloaded.  The secret scalar comes as the caller's SecretScalar (own_host.h), which
+// wipes its host copies when the caller returns, after the final wait; the 32-byte device copy of
+// per-share mode is cleared by a kernel behind the multiplication, on every exit path.
+struct DecStages {
+  const uint8_t* d_msgs = nullptr;  // v as uploaded
+  uint8_t* d_H = nullptr;           // n compressed hashes
+  int32_t* d_st = nullptr;          // the verification's statuses
+  uint8_t* d_g = nullptr;           // n compressed shares
+  int32_t* d_gst = nullptr;         // the multiplication's statuses (per-share mode) or null
+  int32_t* d_hst = nullptr;         // defer_redraw: the hash's redraw flags
+};
+static int dec_stages(hbtc_ctx* c, uint32_t n, const SecretScalar& sk, const uint8_t* u_c48,
+                      const uint8_t* w_c96, const uint8_t* msgs, const uint32_t* offsets,
+                      bool defer_redraw, DecStages* out) {
+  void* d_u;
+  if (defer_redraw) {
+    void *d_msgs, *d_off;
+    G2A* d_cand;
+    int32_t* d_hst;
+    HB_TRY(upload_msgs(c, msgs, offsets[n], &d_msgs));
+    HB_TRY(upload(c, "hash.off", offsets, (size_t)4 * (n + 1), &d_off));
+    HB_TRY(upload(c, "in0", u_c48, (size_t)48 * n, &d_u));
+    HB_TRY(wst(c, "hash.cand", n, &d_cand));
+    HB_TRY(wst(c, "hash.out", (size_t)n * 96, &out->d_H));
+    HB_TRY(wst(c, "hash.st", n, &d_hst));
+    HB_TRY(timed(c, "hash", [&] {
+      return launch_hash_cand(c->stream, n, (const uint8_t*)d_u, (const uint8_t*)d_msgs,
+                              (const uint32_t*)d_off, d_cand);
+    }));
+    HB_TRY(timed(c, "hash", [&] { return launch_g2_clear_cofactor(c->stream, n, d_cand, out->d_H, d_hst); }));
+    out->d_hst = d_hst;
+    out->d_msgs = static_cast<const uint8_t*>(d_msgs);
+  } else {
+    HashKeep hk;
+    HB_TRY(hash_batch_gpu(c, n, u_c48, msgs, offsets, nullptr, &hk));
+    out->d_H = hk.d_out;
+    out->d_msgs = hk.d_msgs;
+    HB_TRY(upload(c, "in0", u_c48, (size_t)48 * n, &d_u));
   }
+  void *d_w, *d_st, *d_g, *d_gst;
+  HB_TRY(upload(c, "in2", w_c96, (size_t)96 * n, &d_w));
+  HB_TRY(ws(c, "out0", (size_t)4 * n, &d_st));
+  HB_TRY(ws(c, "out1", (size_t)48 * n, &d_g));
+  HB_TRY(ws(c, "out2", (size_t)4 * n, &d_gst));
+  // H is this call's own hash output (cofactor cleared: in the subgroup by construction)
+  const bool rlc = c->verify_mode == HBTC_MODE_RLC;
+  G1A* d_adec = nullptr;
+  if (rlc) HB_TRY(wst(c, "dec.adec", n, &d_adec));
+  HB_TRY(pb_verify_dev(c, n, (const uint8_t*)d_u, out->d_H, true, (const uint8_t*)d_w, (int32_t*)d_st,
+                       d_adec));
+  int rc;
+  if (rlc) {
+    // g = sk u on the u decoded by the pair batch, for the ciphertexts that verify:
+    // sk = k0 + k1 x^2 (k0 < x^2), [sk] u = [k0] u + [k1] (beta x, -y)
+    rc = timed(c, "mul", [&] {
+      return launch_pb_mul_glv(c->stream, n, d_adec, (const int32_t*)d_st, sk.k0, sk.k1, (uint8_t*)d_g);
+    });
+    d_gst = nullptr;  // statuses are in d_st
+  } else {
+    void* d_k = nullptr;
+    rc = upload(c, "in3", sk.k, 32, &d_k);  // sk.k lives until the caller's final wait
+    if (rc == HBTC_OK)
+      rc = timed(c, "mul", [&] {
+        return launch_point_mul(c->stream, 1, n, (const uint8_t*)d_u, 1, (const uint8_t*)d_k, 0,
+                                (uint8_t*)d_g, (int32_t*)d_gst);
+      });
+    if (d_k && launch_zero_u32(c->stream, static_cast<uint32_t*>(d_k), 8) != hipSuccess && rc == HBTC_OK)
+      rc = fail(c, HBTC_ERR_DEVICE, "decrypt: the secret scalar's device copy was not cleared");
+  }
+  HB_TRY(rc);
+  out->d_st = static_cast<int32_t*>(d_st);
+  out->d_g = static_cast<uint8_t*>(d_g);
+  out->d_gst = static_cast<int32_t*>(d_gst);
+  return HBTC_OK;
 }
 
 int hbtc_decrypt(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t* u_c48,
@@ -3383,50 +3431,167 @@ int hbtc_decrypt(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t*
   Guard g(c);
   std::vector<uint32_t> blk;
   HB_TRY(pad_block_table(c, n, offsets, blk));  // refuse before anything is enqueued
-  // 1. H_i = hash_g1_g2(u_i, v_i) on the GPU; H and the uploaded v stay there
-  HashKeep hk;
-  HB_TRY(hash_batch_gpu(c, n, u_c48, msgs, offsets, nullptr, &hk));
-  // 2. Ciphertext::verify: e(G1, w) == e(u, H);  3. g = sk * u
-  Fr k;
-  scalar_mod_r(k.v, sk_le32);
-  void *d_u, *d_H = hk.d_out, *d_w, *d_st, *d_k, *d_g, *d_gst, *d_plain;
+  // 1. H = hash_g1_g2(u, v);  2. Ciphertext::verify;  3. g = sk * u
+  const SecretScalar sk(sk_le32);  // wiped when this call returns, behind its final wait
+  DecStages s;
+  HB_TRY(dec_stages(c, n, sk, u_c48, w_c96, msgs, offsets, false, &s));
+  void* d_plain;
   const size_t total = offsets[n];
-  HB_TRY(upload(c, "in0", u_c48, (size_t)48 * n, &d_u));
-  HB_TRY(upload(c, "in2", w_c96, (size_t)96 * n, &d_w));
-  HB_TRY(upload(c, "in3", k.v, 32, &d_k));
-  HB_TRY(ws(c, "out0", (size_t)4 * n, &d_st));
-  HB_TRY(ws(c, "out1", (size_t)48 * n, &d_g));
-  HB_TRY(ws(c, "out2", (size_t)4 * n, &d_gst));
   HB_TRY(ws(c, "out3", total, &d_plain));
-  // H is this call's own hash output (cofactor cleared: in the subgroup by construction)
-  const bool rlc = c->verify_mode == HBTC_MODE_RLC;
-  G1A* d_adec = nullptr;
-  if (rlc) HB_TRY(wst(c, "dec.adec", n, &d_adec));
-  HB_TRY(pb_verify_dev(c, n, (const uint8_t*)d_u, (const uint8_t*)d_H, true, (const uint8_t*)d_w,
-                       (int32_t*)d_st, d_adec));
-  if (rlc) {
-    // g = sk u on the u decoded by the pair batch, for the ciphertexts that verify:
-    // sk = k0 + k1 x^2 (k0 < x^2), [sk] u = [k0] u + [k1] (beta x, -y)
-    uint32_t k0[4], k1[4];
-    split_by_x2(k.v, k0, k1);
-    HB_TRY(timed(c, "mul", [&] {
-      return launch_pb_mul_glv(c->stream, n, d_adec, (const int32_t*)d_st, k0, k1, (uint8_t*)d_g);
-    }));
-    d_gst = nullptr;  // statuses are in d_st
-  } else {
-    HB_TRY(timed(c, "mul", [&] {
-      return launch_point_mul(c->stream, 1, n, (const uint8_t*)d_u, 1, (const uint8_t*)d_k, 0,
-                              (uint8_t*)d_g, (int32_t*)d_gst);
-    }));
-  }
   // 4. plaintext = v XOR hash_bytes(g, |v|) for the ciphertexts that verify (zeros for the
   // others), behind the multiplication: ACCEPT in d_st with a failed multiplication is DECODE_ERR
   const int32_t* d_fst;
-  HB_TRY(dec_pad_dev(c, c->stream, n, (const uint8_t*)d_g, (const int32_t*)d_st, (const int32_t*)d_gst,
-                     offsets, hk.d_msgs, (uint8_t*)d_plain, &d_fst));
+  HB_TRY(dec_pad_dev(c, c->stream, n, s.d_g, s.d_st, s.d_gst, offsets, s.d_msgs, (uint8_t*)d_plain, &d_fst));
   HB_TRY(download(c, status, d_fst, (size_t)4 * n));
   HB_TRY(download(c, out, d_plain, total));
   return sync(c);
+}
+
+// hbtc.h hbtc_decrypt_shares: dec_stages without a wait in the middle, then the output step.
+int hbtc_decrypt_shares(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t* u_c48,
+                        const uint8_t* v, const uint32_t* v_offsets, const uint8_t* w_c96,
+                        uint8_t* out_share_c48, uint8_t* out_H_c96, int32_t* status) {
+  if (!c) return HBTC_ERR_ARG;
+  if (n == 0) return HBTC_OK;
+  if (!sk_le32 || !u_c48 || !w_c96 || !v_offsets || !out_share_c48 || !status ||
+      (v_offsets[n] && !v) || !hash_offsets_ok(n, v_offsets))
+    return HBTC_ERR_ARG;
+  Guard g(c);
+  const SecretScalar sk(sk_le32);  // wiped when this call returns, behind its final wait
+  std::vector<int32_t> flags(n);
+  DecStages s;
+  SpanGuard whole;
+  HB_TRY(sync(c));
+  HB_TRY(span_begin(c, whole.sp));
+  HB_TRY(dec_stages(c, n, sk, u_c48, w_c96, v, v_offsets, true, &s));
+  if (s.d_gst) {
+    // per-share mode: the multiplication ran on every item; keep the ACCEPTed items' shares
+    // (a u that verified has decoded, so the multiplication's status adds nothing)
+    HB_TRY(timed(c, "mul", [&] { return launch_gate_c48(c->stream, n, s.d_st, s.d_g); }));
+  }
+  HB_TRY(span_end(c, whole.sp, "own_dec"));
+  whole.handed = c->timing;
+  HB_TRY(download(c, status, s.d_st, (size_t)4 * n));
+  HB_TRY(download(c, out_share_c48, s.d_g, (size_t)48 * n));
+  if (out_H_c96) HB_TRY(download(c, out_H_c96, s.d_H, (size_t)96 * n));
+  HB_TRY(download(c, flags.data(), s.d_hst, (size_t)4 * n));
+  HB_TRY(sync(c));
+  // [h2] cand = O (probability ~2^-250, never observed): G2::rand draws again.  The host hash
+  // continues the loop exactly, and the existing calls redo those items with that H.
+  std::vector<uint32_t> redo;
+  for (uint32_t i = 0; i < n; ++i)
+    if (flags[i]) redo.push_back(i);
+  if (!redo.empty()) {
+    const uint32_t m = (uint32_t)redo.size();
+    std::vector<uint8_t> H((size_t)96 * m), u((size_t)48 * m), w((size_t)96 * m), gsh((size_t)48 * m);
+    std::vector<int32_t> st(m), gst(m);
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t i = redo[j];
+      hash_g1_g2_c96(u_c48 + 48 * (size_t)i, v + v_offsets[i], v_offsets[i + 1] - v_offsets[i],
+                     H.data() + 96 * (size_t)j);
+      memcpy(u.data() + 48 * (size_t)j, u_c48 + 48 * (size_t)i, 48);
+      memcpy(w.data() + 96 * (size_t)j, w_c96 + 96 * (size_t)i, 96);
+    }
+    void *d_u, *d_H, *d_w, *d_st;
+    HB_TRY(upload(c, "in0", u.data(), (size_t)48 * m, &d_u));
+    HB_TRY(upload(c, "in1", H.data(), (size_t)96 * m, &d_H));
+    HB_TRY(upload(c, "in2", w.data(), (size_t)96 * m, &d_w));
+    HB_TRY(ws(c, "out0", (size_t)4 * m, &d_st));
+    HB_TRY(pb_verify_dev(c, m, (const uint8_t*)d_u, (const uint8_t*)d_H, false, (const uint8_t*)d_w,
+                         (int32_t*)d_st));
+    HB_TRY(download(c, st.data(), d_st, (size_t)4 * m));
+    HB_TRY(sync(c));
+    std::vector<uint8_t> k((size_t)32 * m);
+    for (uint32_t j = 0; j < m; ++j) memcpy(k.data() + 32 * (size_t)j, sk_le32, 32);
+    const int rc = point_mul_host(c, 1, m, u.data(), 1, k.data(), gsh.data(), gst.data());
+    for (size_t b = 0; b < k.size(); ++b) static_cast<volatile uint8_t*>(k.data())[b] = 0;
+    void* d_k;
+    if (ws(c, "in1", k.size(), &d_k) == HBTC_OK) (void)hipMemset(d_k, 0, k.size());  // point_mul_host's copy
+    HB_TRY(rc);
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t i = redo[j];
+      const bool ok = st[j] == HBTC_ACCEPT && gst[j] == HBTC_ACCEPT;
+      status[i] = st[j];
+      if (ok)
+        memcpy(out_share_c48 + 48 * (size_t)i, gsh.data() + 48 * (size_t)j, 48);
+      else
+        memset(out_share_c48 + 48 * (size_t)i, 0, 48);
+      if (out_H_c96) memcpy(out_H_c96 + 96 * (size_t)i, H.data() + 96 * (size_t)j, 96);
+    }
+  }
+  return HBTC_OK;
+}
+
+// hbtc.h hbtc_sign_shares: the candidate draw, then k_sig_share (hbtc_own.hip), one wait.
+int hbtc_sign_shares(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint8_t* msgs,
+                     const uint32_t* offsets, uint8_t* out_sig_c96, uint8_t* out_H_c96) {
+  if (!c) return HBTC_ERR_ARG;
+  if (n == 0) return HBTC_OK;
+  if (!sk_le32 || !offsets || !out_sig_c96 || (offsets[n] && !msgs) || !hash_offsets_ok(n, offsets))
+    return HBTC_ERR_ARG;
+  Guard g(c);
+  const SecretScalar sk(sk_le32);  // wiped when this call returns, behind its final wait
+  HB_TRY(sync(c));
+  void *d_msgs, *d_off;
+  G2A* d_cand;
+  uint8_t *d_H, *d_sig;
+  uint32_t* d_flag;
+  HB_TRY(upload_msgs(c, msgs, offsets[n], &d_msgs));
+  HB_TRY(upload(c, "hash.off", offsets, (size_t)4 * (n + 1), &d_off));
+  HB_TRY(wst(c, "hash.cand", n, &d_cand));
+  HB_TRY(wst(c, "hash.out", (size_t)n * 96, &d_H));
+  HB_TRY(wst(c, "own.sig", (size_t)n * 96, &d_sig));
+  HB_TRY(wst(c, "own.flag", n, &d_flag));
+  SpanGuard whole;
+  HB_TRY(span_begin(c, whole.sp));
+  HB_TRY(timed(c, "hash", [&] {
+    return launch_hash_cand(c->stream, n, nullptr, (const uint8_t*)d_msgs, (const uint32_t*)d_off, d_cand);
+  }));
+  // sk = sum_j d[j] |x|^j, the ψ split's digits
+  HB_TRY(timed(c, "mul", [&] { return launch_sig_share(c->stream, n, d_cand, sk.d, d_H, d_sig, d_flag); }));
+  HB_TRY(span_end(c, whole.sp, "own_sig"));
+  whole.handed = c->timing;
+  std::vector<uint32_t> flag(n);
+  HB_TRY(download(c, out_sig_c96, d_sig, (size_t)96 * n));
+  if (out_H_c96) HB_TRY(download(c, out_H_c96, d_H, (size_t)96 * n));
+  HB_TRY(download(c, flag.data(), d_flag, (size_t)4 * n));
+  HB_TRY(sync(c));
+  // [h2] cand = O (never observed): the host hash continues G2::rand's loop exactly, and the
+  // generic multiplication finishes those items, as hbtc_encrypt does
+  std::vector<uint32_t> redo;
+  for (uint32_t i = 0; i < n; ++i)
+    if (flag[i]) redo.push_back(i);
+  if (!redo.empty()) {
+    const uint32_t m = (uint32_t)redo.size();
+    std::vector<uint8_t> H((size_t)96 * m), k(32), sg((size_t)96 * m);
+    std::vector<int32_t> st(m);
+    for (uint32_t j = 0; j < m; ++j)
+      hash_g2_c96(msgs + offsets[redo[j]], offsets[redo[j] + 1] - offsets[redo[j]], H.data() + 96 * (size_t)j);
+    memcpy(k.data(), sk_le32, 32);
+    void *d_b, *d_k, *d_o, *d_s;
+    int rc = upload(c, "in0", H.data(), (size_t)96 * m, &d_b);
+    if (rc == HBTC_OK) rc = upload(c, "in1", k.data(), 32, &d_k);
+    if (rc == HBTC_OK) rc = ws(c, "out0", (size_t)96 * m, &d_o);
+    if (rc == HBTC_OK) rc = ws(c, "out1", (size_t)4 * m, &d_s);
+    if (rc == HBTC_OK)
+      rc = timed(c, "mul", [&] {
+        return launch_point_mul(c->stream, 2, m, (const uint8_t*)d_b, 1, (const uint8_t*)d_k, 0,
+                                (uint8_t*)d_o, (int32_t*)d_s);
+      });
+    if (rc == HBTC_OK) rc = download(c, sg.data(), d_o, (size_t)96 * m);
+    if (rc == HBTC_OK) rc = download(c, st.data(), d_s, (size_t)4 * m);
+    if (rc == HBTC_OK) (void)launch_zero_u32(c->stream, static_cast<uint32_t*>(d_k), 8);
+    const int rs = sync(c);
+    for (size_t b = 0; b < 32; ++b) static_cast<volatile uint8_t*>(k.data())[b] = 0;
+    HB_TRY(rc);
+    HB_TRY(rs);
+    for (uint32_t j = 0; j < m; ++j) {
+      if (st[j] != HBTC_ACCEPT) return fail(c, HBTC_ERR_DEVICE, "sign_shares: the hash point failed to decode");
+      memcpy(out_sig_c96 + 96 * (size_t)redo[j], sg.data() + 96 * (size_t)j, 96);
+      if (out_H_c96) memcpy(out_H_c96 + 96 * (size_t)redo[j], H.data() + 96 * (size_t)j, 96);
+    }
+  }
+  return HBTC_OK;
 }
 
 int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_stride,

@@ -380,6 +380,13 @@ hipError_t launch_dec_seed(hipStream_t s, uint32_t n, const uint8_t* g_c48, cons
 // w = [r] [h2] cand (compressed) on lane pairs; flag[i] = 1: [h2] cand = O, the host finishes it
 hipError_t launch_enc_w(hipStream_t s, uint32_t n, const G2A* cand, const uint8_t* r_le32,
                         const int32_t* status, uint8_t* out_w, uint32_t* flag);
+// SecretKeyShare::sign (hbtc_own.hip): H = [h2] cand and sigma = [sk] H (both compressed, 16-byte
+// aligned) on lane pairs; d = the four base-|x| digits of the reduced scalar (curve.h
+// gls_u_digits); flag[i] = 1: [h2] cand = O, both outputs zero, the host finishes the item
+hipError_t launch_sig_share(hipStream_t s, uint32_t n, const G2A* cand, const uint64_t* d,
+                            uint8_t* out_h_c96, uint8_t* out_sig_c96, uint32_t* flag);
+// SecretKeyShare::decrypt_share's output gate: g_i := 48 zero bytes where gate[i] != ACCEPT
+hipError_t launch_gate_c48(hipStream_t s, uint32_t n, const int32_t* gate, uint8_t* g_c48);
 // n 256-bit little-endian values -> Montgomery Fr of their residues
 hipError_t launch_fr_to_mont(hipStream_t s, uint64_t n, const uint8_t* in_le32, Fr* out);
 // out[p * n_x + j] = poly_p(x_j), canonical; coeffs / xs in Montgomery form

@@ -11,9 +11,13 @@ reference (coin.rs:105, td.rs:121-123), produce nothing.  Combines triggered dur
 (try_output) are batched too; an instance whose deferred combine fails is replayed again in
 synchronous mode so the reference's retry-on-error behaviour is kept.
 
-Inputs are hbbft's wire encodings (compressed points).  H = hash_g2(nonce) / hash_g1_g2(u, v)
-is supplied by the caller (threshold_crypto on the Rust side, per the design), and so is this
-node's own share (signing is producer-side).  ThresholdDecryption outputs the combined point
+Inputs are hbbft's wire encodings (compressed points).  By default H = hash_g2(nonce) /
+hash_g1_g2(u, v) and this node's own share are supplied by the caller, as before.  With
+``sk_share=`` (this node's secret key share, an int) the queues make both on the GPU instead:
+CoinEpoch's flush signs every instance added with a nonce in ONE ctx.sign_shares call
+(SecretKeyShare::sign, coin.rs:142), and DecryptionEpoch's flush replaces its ciphertext check
+by ONE ctx.decrypt_shares call (SecretKeyShare::decrypt_share, td.rs:98: H, Ciphertext::verify
+and sk u); ``own_share(key)`` is the share to multicast.  ThresholdDecryption outputs the combined point
 g = sum l_i d_i (compressed) by default; DecryptionEpoch(plaintext=True) outputs what the
 reference's try_output does, the plaintext v XOR hash_bytes(g, |v|), made on the GPU behind the
 combine (hbtc_threshold_decrypt).
@@ -42,9 +46,10 @@ class NetInfo:
 
 # ================================================================================== Coin
 class _CoinState:
-    def __init__(self, H, our_share):
+    def __init__(self, H, our_share, nonce=None):
         self.H = H
         self.our_share = our_share
+        self.nonce = nonce
         self.events = []
         self.received = {}
         self.had_input = False
@@ -54,13 +59,39 @@ class _CoinState:
 class CoinEpoch:
     """Every Coin instance (coin.rs:64) of one epoch behind one batch queue."""
 
-    def __init__(self, ctx, netinfo):
+    def __init__(self, ctx, netinfo, *, sk_share=None):
         self.ctx = ctx
         self.ni = netinfo
         self.inst = {}
+        self.sk_share = sk_share
 
-    def add(self, key, H_c96, our_share_c96=None):
-        self.inst[key] = _CoinState(bytes(H_c96), our_share_c96)
+    def add(self, key, H_c96=None, our_share_c96=None, nonce=None):
+        """H_c96 (and our_share_c96 for a validator) from the caller, or, with sk_share set,
+        nonce=...: the next flush makes H = hash_g2(nonce) and the share sk_share H."""
+        if H_c96 is None:
+            if nonce is None or self.sk_share is None:
+                raise ValueError("an instance needs H_c96, or a nonce and the epoch's sk_share")
+            self.inst[key] = _CoinState(None, None, bytes(nonce))
+        else:
+            self.inst[key] = _CoinState(bytes(H_c96), our_share_c96)
+
+    def own_share(self, key):
+        """This node's signature share of the instance (coin.rs:142), None for an observer or
+        before the flush that signs it."""
+        return self.inst[key].our_share if self.ni.is_validator() else None
+
+    def H(self, key):
+        return self.inst[key].H
+
+    def _sign_own(self):
+        todo = [k for k, st in self.inst.items() if st.H is None and st.nonce is not None]
+        if not todo:
+            return
+        sigs, Hs = self.ctx.sign_shares(self.sk_share, [self.inst[k].nonce for k in todo])
+        for k, sg, h in zip(todo, sigs, Hs):
+            self.inst[k].H = h
+            if self.ni.is_validator():
+                self.inst[k].our_share = sg
 
     def handle_input(self, key):
         self.inst[key].events.append(("input",))
@@ -73,6 +104,7 @@ class CoinEpoch:
         """Verify every queued share in one GPU call, replay, batch the combines.  Returns
         {key: [step per queued event]}."""
         ni = self.ni
+        self._sign_own()
         keys = [k for k in self.inst if self.inst[k].events]
         # state at the start of the flush: a failed deferred combine replays from here
         snap = {k: (dict(self.inst[k].received), self.inst[k].had_input, self.inst[k].terminated)
@@ -215,19 +247,33 @@ class DecryptionEpoch:
     plaintext=True: it outputs the plaintext bytes, as try_output does (td.rs:187): the flush's
     pending combines go through ONE ctx.threshold_decrypt call (shares -> g -> plaintext on the
     device) with the v, w and H of each instance's stored ciphertext.  That call verifies the
-    shares it combines once more, this node's own share included."""
+    shares it combines once more, this node's own share included.
 
-    def __init__(self, ctx, netinfo, plaintext=False):
+    sk_share=None: the caller passes H with every ciphertext and this node's share with add().
+    sk_share set: both may be omitted; the flush's ONE ctx.decrypt_shares call over the queued
+    ciphertexts gives their validity, their H and this node's shares."""
+
+    def __init__(self, ctx, netinfo, plaintext=False, *, sk_share=None):
         self.ctx = ctx
         self.ni = netinfo
         self.inst = {}
         self.plaintext = plaintext
+        self.sk_share = sk_share
 
     def add(self, key, our_share_c48=None):
         self.inst[key] = _TdState(our_share_c48)
 
-    def set_ciphertext(self, key, u_c48, v, w_c96, H_c96):
-        self.inst[key].events.append(("ct", (bytes(u_c48), bytes(v), bytes(w_c96), bytes(H_c96))))
+    def set_ciphertext(self, key, u_c48, v, w_c96, H_c96=None):
+        if H_c96 is None and self.sk_share is None:
+            raise ValueError("a ciphertext needs H_c96, or the epoch's sk_share")
+        self.inst[key].events.append(("ct", (bytes(u_c48), bytes(v), bytes(w_c96),
+                                             None if H_c96 is None else bytes(H_c96))))
+
+    def own_share(self, key):
+        """The share to multicast (td.rs:107-108): None before the instance has a valid
+        ciphertext, and for an observer."""
+        st = self.inst[key]
+        return st.our_share if self.ni.is_validator() and st.ct is not None else None
 
     def handle_message(self, key, sender, share_c48):
         self.inst[key].events.append(("msg", sender, bytes(share_c48)))
@@ -243,8 +289,17 @@ class DecryptionEpoch:
             st = self.inst[k]
             if st.ct is None:
                 ct_ev += [(k, e_i, ev[1]) for e_i, ev in enumerate(st.events) if ev[0] == "ct"]
-        ct_ok = {}
-        if ct_ev:
+        ct_ok, own = {}, {}
+        if ct_ev and self.sk_share is not None:
+            # SecretKeyShare::decrypt_share (td.rs:98) of every queued ciphertext in one call
+            g, Hs, vs = self.ctx.decrypt_shares(self.sk_share, [c[0] for _, _, c in ct_ev],
+                                                [c[1] for _, _, c in ct_ev], [c[2] for _, _, c in ct_ev])
+            ct_ev = [(k, e_i, c[:3] + (h,)) for (k, e_i, c), h in zip(ct_ev, Hs)]
+            for (k, e_i, c), v, gi in zip(ct_ev, vs, g):
+                self.inst[k].events[e_i] = ("ct", c)  # H is stored with the ciphertext
+                ct_ok[(k, e_i)] = int(v) == N.ACCEPT
+                own[(k, e_i)] = gi
+        elif ct_ev:
             vs = self.ctx.verify_ciphertexts([c[0] for _, _, c in ct_ev], [c[3] for _, _, c in ct_ev],
                                              [c[2] for _, _, c in ct_ev])
             for (k, e_i, _), v in zip(ct_ev, vs):
@@ -287,7 +342,7 @@ class DecryptionEpoch:
                 verdict[key] = int(status[pos]) == N.ACCEPT
         results, pending = {}, []
         for k in keys:
-            results[k] = self._replay(k, verdict, ct_ok, pending)
+            results[k] = self._replay(k, verdict, ct_ok, pending, own)
         if pending:
             t = ni.num_faulty + 1
             counts = [len(p[2]) for p in pending]
@@ -315,7 +370,7 @@ class DecryptionEpoch:
             return False
         return verdict.get((k, tag, sender), False)
 
-    def _replay(self, k, verdict, ct_ok, pending):
+    def _replay(self, k, verdict, ct_ok, pending, own):
         st, ni = self.inst[k], self.ni
         steps = []
         stored_tag = {s: "stored" for s in st.shares}
@@ -333,6 +388,8 @@ class DecryptionEpoch:
                     del st.shares[s]
                 step = _step(faults=[(s, "UnverifiedDecryptionShareSender") for s in bad])
                 if ni.is_validator():
+                    if (k, e_i) in own:
+                        st.our_share = own[(k, e_i)]
                     st.shares[ni.our_id] = st.our_share
                     stored_tag[ni.our_id] = "own"
                 r = self._try_output(k, pending)

@@ -30,6 +30,10 @@
  *   hbtc_skg_generate        SyncKeyGen::generate + NetworkInfo::new: the era's PublicKeySet, our secret key
  *                            share and every public key share, loaded as a key set
  *                                                                             src/sync_key_gen.rs:428-447, src/messaging.rs:253-256
+ *   hbtc_decrypt_shares      SecretKeyShare::decrypt_share (hash_g1_g2, Ciphertext::verify, sk u) for every
+ *                            accepted proposer's ciphertext   src/threshold_decryption.rs:94-113
+ *   hbtc_sign_shares         SecretKeyShare::sign (hash_g2, sk H): the node's own coin shares
+ *                                                                             src/coin.rs:138-147
  *   hbtc_g1_msm/hbtc_g2_msm  batched Pippenger MSMs (BivarCommitment::row / Commitment::evaluate,
  *                            src/sync_key_gen.rs:345,366,493); the combines run on the same kernels
  *
@@ -260,6 +264,48 @@ int hbtc_skg_generate(hbtc_ctx* ctx, uint32_t n_parts, uint32_t t, const uint8_t
                       const uint32_t* val_offsets, const uint32_t* val_x, const uint8_t* vals_le32,
                       uint32_t n_nodes, uint8_t* out_commit_c48, uint8_t* out_pk_shares_c48,
                       uint8_t* out_sk_le32, uint32_t* out_keyset_id, int32_t* status);
+
+/* ---- this node's own shares ----------------------------------------------------------------- */
+/* SecretKeyShare::decrypt_share for n ciphertexts (u_i, v_i, w_i) under ONE secret key share
+ * (ThresholdDecryption::set_ciphertext, src/threshold_decryption.rs:94-113; epoch_state.rs:363-386).
+ * sk_le32: 32 bytes little-endian, any value below 2^256, taken mod the group order as hbtc_decrypt
+ * does.  v_i = v[v_offsets[i] .. v_offsets[i+1]) (v_offsets[0] == 0, non-decreasing: the offset
+ * rule of the hash batches).
+ *   out_H_c96[96 i ..] = hash_g1_g2(u_i bytes as given, v_i) for EVERY item, whatever its status:
+ *     the bytes hbtc_hash_g1_g2_batch_gpu gives on the same inputs.  May be NULL.
+ *   status[i] is exactly what hbtc_verify_ciphertexts(u, H, w) gives for that item with that H
+ *     under the context's verify mode and hbtc_set_exact_below: ACCEPT; REJECT (decrypt_share
+ *     returns None, set_ciphertext answers InvalidCiphertext); DECODE_ERR (u or w does not decode
+ *     or is outside the subgroup).
+ *   out_share_c48[48 i ..] = the compressed sk u_i for ACCEPT items (byte-equal to hbtc_g1_mul on
+ *     the same u and scalar), 48 zero bytes for every other item.  sk == 0 mod the order, or u the
+ *     point at infinity where it passes, gives the infinity encoding, as the reference's arithmetic.
+ * n == 0 returns HBTC_OK.  HBTC_ERR_ARG: a NULL context; NULL sk_le32, u_c48, w_c96, v_offsets,
+ * out_share_c48 or status; a NULL v with v_offsets[n] != 0, or bad offsets.
+ * The stages of hbtc_decrypt up to its multiplication run back to back on the device (DESIGN.md
+ * "Own shares"): inputs uploaded once, outputs downloaded once, the hash's redraw flags read only
+ * after the final wait (a flagged item, probability ~2^-250, is then redone through the existing
+ * calls).  The pair batch of RLC mode still reads back its 4-byte count of failing items, as in
+ * every call that uses it; the exact checks (per-share mode, fewer items than
+ * hbtc_set_exact_below) wait only at the end.  Every host and device staging copy of the scalar
+ * and of its split digits is overwritten with zeros before the call returns, on every exit path. */
+int hbtc_decrypt_shares(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const uint8_t* u_c48,
+                        const uint8_t* v, const uint32_t* v_offsets, const uint8_t* w_c96,
+                        uint8_t* out_share_c48, uint8_t* out_H_c96, int32_t* status);
+
+/* SecretKeyShare::sign (and SecretKey::sign) for n messages under ONE secret key
+ * (Coin::get_coin, src/coin.rs:142; nonces of binary_agreement/mod.rs:151-166).
+ * msg_i = msgs[offsets[i] .. offsets[i+1]).
+ *   out_H_c96[96 i ..] = hash_g2(msg_i), byte-equal to hbtc_hash_g2_batch_gpu.  May be NULL.
+ *   out_sig_c96[96 i ..] = the compressed sk H_i, byte-equal to hbtc_g2_mul(H_i, sk); sk == 0 mod
+ *     the order gives the infinity encoding.
+ * There is no per-item status: every byte string hashes to a point.  The argument rules are those
+ * of hbtc_decrypt_shares (NULL sk_le32, offsets or out_sig_c96; NULL msgs with offsets[n] != 0; bad
+ * offsets).  One upload, the candidate draw and k_sig_share (cofactor clearing, multiplication and
+ * both encodings on lane pairs, H never leaving the registers in between), one download, one wait;
+ * the scalar and its digits are zeroed as above (they reach the device only as kernel arguments). */
+int hbtc_sign_shares(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const uint8_t* msgs,
+                     const uint32_t* offsets, uint8_t* out_sig_c96, uint8_t* out_H_c96);
 
 /* ---- host hashes (no context, no GPU) ----------------------------------------------------- */
 /* threshold_crypto's crate-internal hash_g2(msg) -> compressed G2 (96 B), and hash_g1_g2(g1, msg)
@@ -641,7 +687,11 @@ int hbtc_merkle_validate_dev(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const 
  * "merkle_validate", "dec_pad" (k_dec_seed + k_enc_pad behind a combine or hbtc_decrypt's
  * multiplication), "keygen" (hbtc_skg_generate, the whole call on the device) and its stages
  * "keygen_sum" (row0 decode + column sums), "keygen_sk" (the interpolations), "keygen_shares"
- * (commitment evaluation); its key-set tables count under "prepare".  Reading
+ * (commitment evaluation); its key-set tables count under "prepare"; "own_dec"
+ * (hbtc_decrypt_shares) and "own_sig" (hbtc_sign_shares), each the whole call on the device, their
+ * stages counting under "hash", the pair check's families ("pb_items", "pb_lines", "pb_ml",
+ * "pb_checks" of the pair batch; "pb_decode", "sig_items", "chk_leaves" of the exact checks) and
+ * "mul".  Reading
  * synchronises the stream. */
 int hbtc_timing_enable(hbtc_ctx* ctx, int enable);
 int hbtc_timing_read(hbtc_ctx* ctx, const char* family, double* total_ms, uint64_t* launches);

@@ -296,6 +296,43 @@ impl Context {
         Ok((u, v, w, st))
     }
 
+    /// SecretKeyShare::decrypt_share for a batch under one secret key share
+    /// (ThresholdDecryption::set_ciphertext, src/threshold_decryption.rs:94-113): (shares, H, status).
+    /// H[96 i ..] = hash_g1_g2(u_i, v_i) for every item; shares[48 i ..] = sk u_i where status[i] is
+    /// ACCEPT and 48 zero bytes elsewhere (REJECT: decrypt_share returns None).  Written against the
+    /// C ABI and, like the rest of this crate, not compiled in this repository's checks.
+    pub fn decrypt_shares(&self, sk_le32: &[u8; 32], u_c48: &[u8], v: &[u8], v_offsets: &[u32], w_c96: &[u8])
+        -> Result<(Vec<u8>, Vec<u8>, Vec<i32>)> {
+        assert!(!v_offsets.is_empty() && v_offsets[0] == 0, "v_offsets[0] must be 0");
+        assert!(v_offsets.windows(2).all(|w| w[0] <= w[1]), "v_offsets must be non-decreasing");
+        let n = v_offsets.len() - 1;
+        assert!(v_offsets[n] as usize <= v.len(), "v_offsets past the bytes of v");
+        assert_eq!(u_c48.len(), 48 * n, "one compressed G1 u per ciphertext");
+        assert_eq!(w_c96.len(), 96 * n, "one compressed G2 w per ciphertext");
+        let (mut g, mut h, mut st) = (vec![0u8; 48 * n], vec![0u8; 96 * n], vec![0i32; n]);
+        self.ok(unsafe {
+            ffi::hbtc_decrypt_shares(self.raw, n as u32, sk_le32.as_ptr(), u_c48.as_ptr(), v.as_ptr(),
+                                     v_offsets.as_ptr(), w_c96.as_ptr(), g.as_mut_ptr(), h.as_mut_ptr(),
+                                     st.as_mut_ptr())
+        })?;
+        Ok((g, h, st))
+    }
+
+    /// SecretKeyShare::sign for a batch of messages under one secret key (share) (Coin::get_coin,
+    /// src/coin.rs:142): (signatures, H) with H[96 i ..] = hash_g2(msg_i) and sig_i = sk H_i.
+    pub fn sign_shares(&self, sk_le32: &[u8; 32], msgs: &[u8], offsets: &[u32]) -> Result<(Vec<u8>, Vec<u8>)> {
+        assert!(!offsets.is_empty() && offsets[0] == 0, "offsets[0] must be 0");
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]), "offsets must be non-decreasing");
+        let n = offsets.len() - 1;
+        assert!(offsets[n] as usize <= msgs.len(), "offsets past the message bytes");
+        let (mut sig, mut h) = (vec![0u8; 96 * n], vec![0u8; 96 * n]);
+        self.ok(unsafe {
+            ffi::hbtc_sign_shares(self.raw, n as u32, sk_le32.as_ptr(), msgs.as_ptr(), offsets.as_ptr(),
+                                  sig.as_mut_ptr(), h.as_mut_ptr())
+        })?;
+        Ok((sig, h))
+    }
+
     /// out[p * n_x + j] = poly_p(x_j) over Fr (32-byte LE each): n_poly rows of n_coeff coefficients.
     pub fn fr_poly_eval(&self, n_coeff: u32, coeffs_le32: &[u8], x_le32: &[u8]) -> Result<Vec<u8>> {
         assert_eq!(x_le32.len() % 32, 0);

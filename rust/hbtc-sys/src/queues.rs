@@ -12,8 +12,10 @@
 //! instance whose deferred combine fails is replayed again with synchronous combines, which keeps
 //! the reference's retry-on-error behaviour (`src/coin.rs:163-181`).
 //!
-//! H = hash_g2(nonce) / hash_g1_g2(u, v) is supplied by the caller (`hash_g2` of this crate, or
-//! `hbtc_hash_*_batch_gpu` for a whole epoch), and so is this node's own share.
+//! These queues take H = hash_g2(nonce) / hash_g1_g2(u, v) and this node's own share from the
+//! caller.  `Context::sign_shares` (H and the coin share of every nonce) and
+//! `Context::decrypt_shares` (H, the ciphertext's validity and the decryption share of every
+//! ciphertext) produce them on the GPU for a whole epoch.
 
 use std::collections::{BTreeMap, BTreeSet};
 
