@@ -151,6 +151,15 @@ resources-rlc:
 	for p in 6 7; do $(HIPCC) $(HIPFLAGS) -DHBTC_PART=$$p -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE $(RLC_FLAGS) -c $(CSRC)/hbtc_rlc.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"; done
 
+# the MSM kernels (k_msm_buckets and its neighbours) with the flags of hbtc_msm.p8.o / p9.o;
+# MSM_FLAGS=-DHBTC_MSM_WALK=0 reports the nested-loop walk
+.PHONY: resources-msm
+resources-msm:
+	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=8 -DHBTC_FQMUL_INLINE -DHBTC_INLINE_ALL $(MSM_FLAGS) -c $(CSRC)/hbtc_msm.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
+	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=9 -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR $(MSM_FLAGS) -c $(CSRC)/hbtc_msm.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
+
 .PHONY: resources-enc
 resources-enc:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
@@ -168,7 +177,17 @@ resources-own:
 
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
-          tests/native/libhbtc_own_hosttest.so
+          tests/native/libhbtc_own_hosttest.so tests/native/libhbtc_msm_hosttest.so
+# msm_walk.h's host build (one wave of the lane-uniform bucket walk in lockstep, over a toy group
+# and over G1)
+tests/native/libhbtc_msm_hosttest.so: tests/native/hbtc_msm_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_msm_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-msm
+sanitize-msm: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_msm_host_main.cpp tests/native/hbtc_msm_hosttest.cpp -o $(BUILD)/msm_host_asan
+	$(BUILD)/msm_host_asan
 # own_host.h's host build (the secret scalar of hbtc_decrypt_shares / hbtc_sign_shares: reduction,
 # the x^2 split, the base-|x| digits, the wiping)
 tests/native/libhbtc_own_hosttest.so: tests/native/hbtc_own_hosttest.cpp $(HDRS)

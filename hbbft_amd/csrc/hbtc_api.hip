@@ -1160,6 +1160,15 @@ int sig_shares_dev(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uint8
 // Window width of a batch of n-term MSMs of scalars < 2^bits: minimise W * (mixed adds + bucket
 // adds) in Fqm (mixed add 11, full add 16, segment scaling ~15 per bit per 8 buckets), W =
 // ceil((bits + 1) / c) windows (the signed recoding's last carry needs the extra bit).
+// Under the lane-uniform walk (msm_walk.h) the terms read: 11 n, the wave's mixed additions (its
+// longest slice is within a term of 8n/B); 16 B = 8 rank sums on each of the S = B/8 segment lanes;
+// 15 c B/8, the multiple [B - r_last] run at the wave's longest chain.  What a wave issues is
+// (tools/msm_walk_model.py) 8 + 470 / (8n/B + 12) flush rounds instead of 8 -- 9.4 at slices of 328
+// terms, 13.1 at 84, 16.7 at 42 -- and 22 (c - 1) - 20 Fqm for the multiple instead of 15 c.  With
+// those terms the minimum moves one width down near the thresholds (n = 668, 128 bits: 6 instead of
+// 7, 184 k against 188 k Fqm per MSM); C3 measured the same epoch at both and a slower one at 8
+// (DESIGN.md §5 round 10), and no other shape was timed at a width of its own, so the terms that
+// choose the width stay.
 uint32_t msm_window(uint32_t n, uint32_t bits = 255) {
   uint32_t best = 4;
   double best_cost = 1e300;
@@ -1175,7 +1184,9 @@ uint32_t msm_window(uint32_t n, uint32_t bits = 255) {
 }
 
 // Window width by the LONGEST per-lane chain instead (in Fqm): a segment thread of
-// k_msm_buckets walks 8n/B list terms (mixed adds), 8 rank sums and a small multiple; k_msm_wsum
+// k_msm_buckets walks 8n/B list terms (mixed adds), 8 rank sums (flush rounds of the lane-uniform
+// walk: 8 + 470 / (8n/B + 12) on a full wave, fewer on the few waves of a small batch) and a small
+// multiple; k_msm_wsum
 // adds S = B/8 segments; k_msm_final runs (bits + 1) doublings and W adds.  For batches too small
 // to fill the GPU the combine's time is this chain, not the total work.
 uint32_t msm_window_latency(uint32_t n, uint32_t bits) {
@@ -1200,6 +1211,9 @@ MsmPlan msm_plan(uint32_t n_msm, uint32_t n, uint32_t bits = 255) {
   if (bits <= 128) {  // the φ / ψ-split combines: short scalars, often latency-bound batches
     const uint64_t lanes = (uint64_t)n_msm * ((bits + p.c) / p.c) * std::max(1u, (1u << (p.c - 1)) / 8);
     if (lanes < 65536) p.c = msm_window_latency(n, bits);
+#ifdef HBTC_MSM_C128  // variant builds: a fixed width for the split combines
+    p.c = HBTC_MSM_C128;
+#endif
   }
   p.W = (bits + p.c) / p.c;
   return p;

@@ -33,6 +33,7 @@
 //   roff   [m][w][r]      u32 start of bucket rank r (rank 0 = bucket 2^(c-1)), r = 0..B
 //   part   [m][w][s]      Jac<F> segment partial sums;  wsum [m][w] Jac<F>
 #include "hbtc_kernels.h"
+#include "msm_walk.h"
 #include "pair.h"
 
 #ifndef HBTC_PART
@@ -549,17 +550,33 @@ template __global__ void k_msm_gather<G2A>(uint32_t, uint32_t, const uint32_t*, 
                                            const G2A*, G2A*);
 #endif  // part 8
 
-// Rank whose bucket holds sorted position p: the largest r < B with ro[r] <= p (ro[0] = 0 and
-// p < ro[B]).
-__device__ __forceinline__ uint32_t msm_rank(const uint32_t* ro, uint32_t B, uint32_t p) {
-  uint32_t lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (ro[mid] <= p) lo = mid;
-    else hi = mid;
+#if HBTC_MSM_WALK
+// The snapshot slots of msm_walk.h in LDS, word-interleaved over the wave's lanes ([slot][word][lane]:
+// a wave's access to one word is one conflict-free row).  MSM_SLOTS points per lane, 64 lanes per
+// workgroup: bounded by the launch geometry, not by the number of MSMs of the call.
+template <class J>
+struct WalkLds {
+  static constexpr int NW = (int)(sizeof(J) / 4);
+  uint32_t* lds;  // the lane's column
+  __device__ __forceinline__ void put(uint32_t k, const J& p) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&p);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) lds[(k * NW + j) * 64] = src[j];
   }
-  return lo;
+  __device__ __forceinline__ void get(J& p, uint32_t k) const {
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&p);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) dst[j] = lds[(k * NW + j) * 64];
+  }
+};
+// One flush of the wave: round k while any lane has more than k snapshots pending
+template <class J, class St>
+__device__ __forceinline__ void msm_walk_flush(MsmWalk& w, J& tot, const St& st) {
+#pragma unroll 1
+  for (uint32_t k = 0; k < MSM_SLOTS && __any(walk_pending(w) > k); ++k) walk_flush(w, k, tot, st);
+  walk_flush_done(w);
 }
+#endif
 
 // One lane per (msm, window, segment): S = B/8 segments split the window's sorted nonzero terms
 // into equal slices of the LIST (not of the buckets), so a window whose digits crowd into a few
@@ -586,6 +603,34 @@ __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_BUCKET
   // pts_map: MSMs sharing one decoded point set (several Ack equations over one commitment)
   const uint64_t blk = pts_map ? (uint64_t)pts_map[mw / W] : mw / W;
   const Aff<F>* P = pts + blk * n;
+#if HBTC_MSM_WALK
+  // the lane-uniform walk (msm_walk.h): one loop over the slice's positions, rank boundaries
+  // deferred through the lane's snapshot slots in LDS, the wave flushing together
+  __shared__ uint32_t snap[MSM_SLOTS * WalkLds<Jac<F>>::NW * 64];
+  WalkLds<Jac<F>> st{snap + threadIdx.x};
+  Jac<F> run, tot;
+  jac_set_inf(run);
+  jac_set_inf(tot);
+  MsmWalk w;
+  walk_begin(w, ro, B, S, s);
+#pragma unroll 1
+  for (;;) {
+    const bool need = walk_boundary(w, ro, run, st, MSM_SLOTS);
+    if (__any(need)) {
+      msm_walk_flush(w, tot, st);
+      continue;
+    }
+    if (!__any(walk_active(w))) break;
+    if (walk_active(w)) {
+      const uint32_t v = L[walk_step(w)];
+      Aff<F> q = P[v & 0x7fffffffu];
+      if (v >> 31) fneg(q.y, q.y);
+      jac_add_aff(run, run, q);
+    }
+  }
+  msm_walk_flush(w, tot, st);
+  walk_finish(tot, run, w, B);
+#else
   Jac<F> run, tot;
   jac_set_inf(run);
   jac_set_inf(tot);
@@ -612,6 +657,7 @@ __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_BUCKET
       jac_add(tot, tot, m);
     }
   }
+#endif
   part[g] = tot;
 }
 
@@ -731,6 +777,32 @@ __global__ void __launch_bounds__(64, HBTC_MSM_G2P_BUCKET_WAVES)
   G2Jp run, tot;
   jac_set_inf(run);
   jac_set_inf(tot);
+#if HBTC_MSM_WALK
+  // the lane-uniform walk (msm_walk.h), both lanes of a pair in the same state; a lane's slot holds
+  // its component of the snapshot
+  __shared__ uint32_t snap[MSM_SLOTS * WalkLds<G2Jp>::NW * 64];
+  WalkLds<G2Jp> st{snap + threadIdx.x};
+  MsmWalk w;
+  walk_begin(w, ro, B, S, s);
+#pragma unroll 1
+  for (;;) {
+    const bool need = walk_boundary(w, ro, run, st, MSM_SLOTS);
+    if (__any(need)) {
+      msm_walk_flush(w, tot, st);
+      continue;
+    }
+    if (!__any(walk_active(w))) break;
+    if (walk_active(w)) {
+      const uint32_t v = L[walk_step(w)];
+      G2Ap q;
+      g2p_load_aff(q, P + (v & 0x7fffffffu));
+      if (v >> 31) fneg(q.y, q.y);
+      jac_add_aff(run, run, q);
+    }
+  }
+  msm_walk_flush(w, tot, st);
+  walk_finish(tot, run, w, B);
+#else
   const uint32_t total = ro[B];
   const uint32_t p0 = (uint32_t)((uint64_t)total * s / S);
   const uint32_t p1 = (uint32_t)((uint64_t)total * (s + 1) / S);
@@ -755,6 +827,7 @@ __global__ void __launch_bounds__(64, HBTC_MSM_G2P_BUCKET_WAVES)
       jac_add(tot, tot, m);
     }
   }
+#endif
   g2p_store_jac(part + g, tot);
 }
 
