@@ -1283,6 +1283,9 @@ HD void fq_to_be_words(uint32_t* w, const Fq& a) {
 enum : uint32_t { FLAG_COMPRESSED = 0x80u, FLAG_INFINITY = 0x40u, FLAG_LARGEST = 0x20u };
 
 // G1Compressed::into_affine.  w = the 48 input bytes as 12 little-endian-loaded words.
+// RR: the square root on 13 limbs of 30 bits (field.h fq_sqrt_rr); the point coming out is
+// canonical either way, so both forms write the same bytes.
+template <bool RR = false>
 HDN bool g1_decompress(G1A& out, const uint32_t* w_in, bool check_subgroup = true) {
   uint32_t w[12];
 #pragma unroll
@@ -1310,7 +1313,7 @@ HDN bool g1_decompress(G1A& out, const uint32_t* w_in, bool check_subgroup = tru
   fq_mul(rhs, rhs, x);
   fq_set(b, G1_B);
   fq_add(rhs, rhs, b);
-  if (!fq_sqrt(y, rhs)) return false;
+  if (!(RR ? fq_sqrt_rr(y, rhs) : fq_sqrt(y, rhs))) return false;
   // choose y if (y < -y) ^ greatest, else -y   (pairing 0.14 get_point_from_x)
   const bool y_largest = fq_is_lex_largest(y);  // y > -y
   if (y_largest != greatest) fq_neg(y, y);

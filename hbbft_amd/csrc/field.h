@@ -70,6 +70,13 @@
 #if defined(HBTC_FQMUL_SR)
 #include "fq_fips_sr.h"
 #endif
+// The product and squaring on 13 limbs of 30 bits (tools/gen_fq_rr.py): no carry word per MAC.
+// HBTC_FQ_RR=1 runs the square root of k_rlc_decode's G1 decode on it (FqR below); 0 builds the
+// 12 x 32 code everywhere, for comparisons.
+#ifndef HBTC_FQ_RR
+#define HBTC_FQ_RR 1
+#endif
+#include "fq_rr.h"
 
 #ifndef HBTC_FQ_UNROLL
 #define HBTC_FQ_UNROLL 1
@@ -663,6 +670,119 @@ HD bool fq_sqrt(Fq& r, const Fq& a) {
   fq_sqr(y2, y);
   r = y;
   return fq_eq(y2, a);
+}
+
+// ------------------------------------------------------- Fq on 13 limbs of 30 bits (fq_rr.h)
+// FqR holds a R' mod p (R' = 2^390) on limbs below 2^30.  A product of the 12 x 32 form issues a
+// 4-cycle v_addc_co_u32 beside every v_mad_u64_u32; here a column's terms add into the MAD's 64-bit
+// addend with no carry word (tools/gen_fq_rr.py: the column bounds and the five overflow splits),
+// 1.42x the products and 1.39x the squarings per second at three waves per SIMD
+// (profiles/r11/fq_rr/).  Bounds: operands < 16p give a result < 1.5p, so chains of fqr_mul /
+// fqr_sqr need no subtraction; fqr_from_fq and fqr_to_fq are a re-limbing and one product each
+// (by R'^2 / R and by R), the value coming out < 1.5p < 2p like every Fq.
+typedef Limbs<13> FqR;
+HD void fqr_mul(FqR& r, const FqR& a, const FqR& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  rr::mont_mul_asm(r.v, a.v, b.v);
+#else
+  rr::mont_mul_cxx(r.v, a.v, b.v);
+#endif
+}
+HD void fqr_sqr(FqR& r, const FqR& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  rr::mont_sqr_asm(r.v, a.v);
+#else
+  rr::mont_sqr_cxx(r.v, a.v);
+#endif
+}
+// the same integer on the other limb size (a < 2^384 going in; limbs < 2^30 and value < 2^384 back)
+HD void fqr_limbs30(FqR& r, const Fq& a) {
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    const int w = (30 * i) >> 5, s = (30 * i) & 31;
+    const uint64_t t = (uint64_t)a.v[w] | (w + 1 < 12 ? (uint64_t)a.v[w + 1] << 32 : 0ull);
+    r.v[i] = (uint32_t)(t >> s) & rr::RR_MASK;
+  }
+}
+HD void fqr_limbs32(Fq& r, const FqR& a) {
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    const int l = (32 * j) / 30, o = (32 * j) % 30;
+    const uint64_t t = (uint64_t)a.v[l] | (l + 1 < 13 ? (uint64_t)a.v[l + 1] << 30 : 0ull) |
+                       (l + 2 < 13 ? (uint64_t)a.v[l + 2] << 60 : 0ull);
+    r.v[j] = (uint32_t)(t >> o);
+  }
+}
+HD void fqr_from_fq(FqR& r, const Fq& a) {  // a R (< 2p) -> a R' (< 1.5p)
+  FqR t, k;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) k.v[i] = rr::RR_K_IN[i];
+  fqr_limbs30(t, a);
+  fqr_mul(r, t, k);
+}
+HD void fqr_to_fq(Fq& r, const FqR& a) {  // a R' (< 16p) -> a R (< 1.5p)
+  FqR t, k;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) k.v[i] = rr::RR_K_OUT[i];
+  fqr_mul(t, a, k);
+  fqr_limbs32(r, t);
+}
+HD void fqr_sel(FqR& r, bool c, const FqR& a, const FqR& b) {
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = c ? a.v[i] : b.v[i];
+}
+// the residue below p, for a < 2p with limbs < 2^30: a - p by a borrow ripple over the 30-bit limbs
+HD void fqr_canon(FqR& r, const FqR& a) {
+  uint32_t t[13], borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    const uint32_t d = a.v[i] - rr::RR_P[i] - borrow;  // in (-2^30 - 1, 2^30): bit 31 is the sign
+    borrow = d >> 31;
+    t[i] = d & rr::RR_MASK;
+  }
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = borrow ? a.v[i] : t[i];
+}
+HD bool fqr_eq(const FqR& a, const FqR& b) {
+  FqR ca, cb;
+  fqr_canon(ca, a);
+  fqr_canon(cb, b);
+  uint32_t d = 0;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) d |= ca.v[i] ^ cb.v[i];
+  return d == 0;
+}
+// fq_pow_window on FqR: the same plan, the table of odd powers in the 30-bit form
+HDN void fqr_pow_window(FqR& r, const FqR& a, const PowPlan& pl) {
+  FqR t[POW_TAB], a2;
+  t[0] = a;
+  fqr_sqr(a2, a);
+#pragma unroll
+  for (int k = 1; k < POW_TAB; ++k) fqr_mul(t[k], t[k - 1], a2);
+  FqR acc = t[0];
+#pragma unroll
+  for (int k = 1; k < POW_TAB; ++k) fqr_sel(acc, pl.first == k, t[k], acc);
+#pragma unroll 1
+  for (int k = 0; k < pl.n; ++k) {
+    const PowStep st = pl.s[k];
+#pragma unroll 1
+    for (int q = 0; q < st.nsq; ++q) fqr_sqr(acc, acc);
+#pragma unroll
+    for (int j = 0; j < POW_TAB; ++j)
+      if (st.idx == j) fqr_mul(acc, acc, t[j]);
+  }
+  r = acc;
+}
+// fq_sqrt with the power, the product by a and the check y^2 == a on FqR; a and r are Fq (12 x 32
+// Montgomery).  r is congruent to fq_sqrt's but may be the other representative below 2p.
+HD bool fq_sqrt_rr(Fq& r, const Fq& a) {
+  FqR ar, t, y, y2;
+  fqr_from_fq(ar, a);
+  fqr_pow_window(t, ar, POW_SQRT_PLAN);  // a^((p-3)/4)
+  fqr_mul(y, t, ar);                     // a^((p+1)/4)
+  fqr_sqr(y2, y);
+  fqr_to_fq(r, y);
+  return fqr_eq(y2, ar);
 }
 
 // canonical(a) > (p-1)/2   <=>  a > -a  (pairing 0.14 ordering on canonical values, a != 0)

@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(64, HBTC_RLC_DEC_WAVES) k_rlc_decode(
     uint32_t w[12];
     rlc_load_words(w, shares, item, 12);
     G1A d;
-    if (!g1_decompress(d, w, false)) {
+    if (!g1_decompress<HBTC_FQ_RR != 0>(d, w, false)) {
       st = HBTC_DECODE_ERR;
     } else if (!d.inf) {
       // the subgroup test (curve.h g1_in_subgroup_t1) with its operands parked in the outputs:

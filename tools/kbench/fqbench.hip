@@ -1,7 +1,8 @@
 // Fq Montgomery-multiplication shape microbenchmark for gfx950 (tool, not product code).
 // Variants: rolled CIOS (round-1 default), fully unrolled CIOS, and product-scanning (FIPS)
 // with the 64-bit multiply-add's carry-out feeding a 32-bit column-overflow counter
-// (grouped inline-asm MACs).  Prints time, Fqm/s and the fraction of the measured
+// (grouped inline-asm MACs), and the carry-free 13 x 30 product / squaring of fq_rr.h against the
+// one-block 12 x 32 forms at 1 / 2 / 3 waves per SIMD.  Prints time, Fqm/s and the fraction of the measured
 // v_mad_u64_u32 roofline (29.51e12 / 288 Fqm/s), plus a cross-check of the three results.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -47,6 +48,39 @@ __global__ void __launch_bounds__(256, WAVES) k_mul(const Fq* in, Fq* out) {
 #pragma unroll
     for (int l = 0; l < 12; ++l) x[0].v[l] ^= x[j].v[l];
   out[i] = x[0];
+}
+
+// The product / squaring of fq_rr.h on field.h's FqR (13 limbs of 30 bits): V 0 product, 1 squaring.
+template <int V>
+__device__ __forceinline__ void mulr(FqR& r, const FqR& a, const FqR& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (V == 0) rr::mont_mul_asm(r.v, a.v, b.v);
+  else rr::mont_sqr_asm(r.v, a.v);
+#endif
+}
+template <int V, int ILP, int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_mul_rr(const FqR* in, FqR* out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  FqR x[ILP];
+  const FqR y = in[(i + 1) & 1023];
+#pragma unroll
+  for (int j = 0; j < ILP; ++j) x[j] = in[(i + 7 * j) & 1023];
+#pragma unroll 1
+  for (int it = 0; it < ITERS; ++it)
+#pragma unroll
+    for (int j = 0; j < ILP; ++j) mulr<V>(x[j], x[j], y);
+#pragma unroll
+  for (int j = 1; j < ILP; ++j)
+#pragma unroll
+    for (int l = 0; l < 13; ++l) x[0].v[l] ^= x[j].v[l];
+  out[i] = x[0];
+}
+template <int V>
+__global__ void k_check_rr(const FqR* in, FqR* out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  FqR r;
+  mulr<V>(r, in[i], in[(i * 7 + 3) & 1023]);
+  out[i] = r;
 }
 
 template <int V>
@@ -103,6 +137,34 @@ int main() {
   }
   printf("cross-check vs host CIOS: products %s (%d limb mismatches), squarings %s (%d)\n",
          bad ? "FAIL" : "ok", bad, bad_sq ? "FAIL" : "ok", bad_sq);
+  // the reduced-radix forms: limbs < 2^30, values < 2^384 < 16p; bit-for-bit against the same
+  // schedule in plain C++ (rr::mont_mul_cxx / mont_sqr_cxx)
+  std::vector<FqR> hr13(1024);
+  for (auto& f : hr13) {
+    for (int l = 0; l < 13; ++l) { s = s * 6364136223846793005ull + 1442695040888963407ull; f.v[l] = (uint32_t)(s >> 34); }
+    f.v[12] &= 0x00ffffffu;
+  }
+  FqR *d_in13, *d_out13;
+  CHK(hipMalloc(&d_in13, sizeof(FqR) * 1024));
+  CHK(hipMalloc(&d_out13, sizeof(FqR) * nthreads));
+  CHK(hipMemcpy(d_in13, hr13.data(), sizeof(FqR) * 1024, hipMemcpyHostToDevice));
+  {
+    std::vector<FqR> got(1024);
+    int bad_rr[2] = {0, 0};
+    for (int v = 0; v < 2; ++v) {
+      if (v == 0) hipLaunchKernelGGL(k_check_rr<0>, dim3(16), dim3(64), 0, 0, d_in13, d_out13);
+      else hipLaunchKernelGGL(k_check_rr<1>, dim3(16), dim3(64), 0, 0, d_in13, d_out13);
+      CHK(hipMemcpy(got.data(), d_out13, sizeof(FqR) * 1024, hipMemcpyDeviceToHost));
+      for (int i = 0; i < 1024; ++i) {
+        FqR want;
+        if (v == 0) rr::mont_mul_cxx(want.v, hr13[i].v, hr13[(i * 7 + 3) & 1023].v);
+        else rr::mont_sqr_cxx(want.v, hr13[i].v);
+        for (int l = 0; l < 13; ++l) bad_rr[v] += got[i].v[l] != want.v[l];
+      }
+    }
+    printf("cross-check 13x30 vs host schedule: product %s (%d limb mismatches), squaring %s (%d)\n",
+           bad_rr[0] ? "FAIL" : "ok", bad_rr[0], bad_rr[1] ? "FAIL" : "ok", bad_rr[1]);
+  }
   hipEvent_t a, b;
   CHK(hipEventCreate(&a));
   CHK(hipEventCreate(&b));
@@ -112,6 +174,19 @@ int main() {
     CHK(hipDeviceSynchronize());
     CHK(hipEventRecord(a));
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d_in, d_out);
+    CHK(hipEventRecord(b));
+    CHK(hipEventSynchronize(b));
+    float ms;
+    CHK(hipEventElapsedTime(&ms, a, b));
+    const double fqm = (double)blocks * 256 * ITERS * ilp;
+    printf("%-40s blocks=%5d %8.3f ms %9.3e Fqm/s %.3f of mad roofline  %.1f ns/Fqm/wave\n", name, blocks, ms,
+           fqm / (ms * 1e-3), fqm / (ms * 1e-3) / peak, ms * 1e6 / (ITERS * ilp));
+  };
+  auto run13 = [&](const char* name, auto kern, int blocks, int ilp) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d_in13, d_out13);
+    CHK(hipDeviceSynchronize());
+    CHK(hipEventRecord(a));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d_in13, d_out13);
     CHK(hipEventRecord(b));
     CHK(hipEventSynchronize(b));
     float ms;
@@ -134,5 +209,15 @@ int main() {
   RUNV(5, "sqr one-block asm")
   RUNV(6, "FIPS subroutine (s_swappc)")
   RUNV(7, "sqr subroutine (s_swappc)")
+  // 13 x 30 (fq_rr.h) against the one-block 12 x 32 forms above, the same run, 1 / 2 / 3 waves
+  // per SIMD (k_rlc_decode runs at 3)
+#define RUNW(KERN, V, NAME, RUN)                          \
+  RUN(NAME " ILP1 1w/SIMD", (KERN<V, 1, 1>), 256, 1);     \
+  RUN(NAME " ILP1 2w/SIMD", (KERN<V, 1, 2>), 512, 1);     \
+  RUN(NAME " ILP1 3w/SIMD", (KERN<V, 1, 3>), 768, 1);
+  RUNW(k_mul, 3, "A/B 12x32 product (one-block asm)", run)
+  RUNW(k_mul_rr, 0, "A/B 13x30 product (fq_rr.h)", run13)
+  RUNW(k_mul, 5, "A/B 12x32 squaring (one-block asm)", run)
+  RUNW(k_mul_rr, 1, "A/B 13x30 squaring (fq_rr.h)", run13)
   return 0;
 }
