@@ -586,6 +586,44 @@ class Context:
                                               _ptr(out), _ptr(st)), "hbtc_combine_dec")
         return [bytes(out[48 * k:48 * k + 48]) for k in range(n)], st
 
+    def _combine_verified(self, fn, what, size, counts, idx, items, status, t, parity):
+        off = _offsets(counts, False)
+        n = off.size - 1
+        ix = np.ascontiguousarray(idx, dtype=np.uint32)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        sb = _join(items, size)
+        if not (ix.size == st.size == sb.size // size == int(off[-1])):
+            raise ValueError("one index, status and share per item")
+        out, par, cst = np.zeros(size * n, np.uint8), np.zeros(max(n, 16), np.uint8), np.empty(n, np.int32)
+        bufs = [self.dev_alloc(a.nbytes) for a in (ix, sb, st, out, par, cst)]
+        try:
+            for p, a in zip(bufs[:3], (ix, sb, st)):
+                if a.nbytes:
+                    self.dev_upload(p, a)
+            args = [self.h, n, _ptr(off)] + bufs[:3] + [t, bufs[3]] + ([bufs[4]] if parity else []) + [bufs[5]]
+            self._check(fn(*args), what)
+            for p, a in zip(bufs[3:], (out, par, cst)):
+                if a.nbytes:
+                    self.dev_download(a, p)
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+        return [bytes(out[size * k:size * (k + 1)]) for k in range(n)], par[:n], cst
+
+    def combine_sigs_verified(self, counts, idx, sigs, status, t):
+        """hbtc.h hbtc_combine_sigs_verified_dev on host data: the first t items of each instance
+        whose status (one int32 per item, as a verification writes it) is ACCEPT are combined; such
+        items must be valid points.  Returns (signatures, parity, inst_status)."""
+        return self._combine_verified(self.lib.hbtc_combine_sigs_verified_dev, "hbtc_combine_sigs_verified_dev",
+                                      96, counts, idx, sigs, status, t, True)
+
+    def combine_dec_verified(self, counts, idx, shares, status, t):
+        """hbtc.h hbtc_combine_dec_verified_dev on host data; returns (g, inst_status)."""
+        g, _, cst = self._combine_verified(self.lib.hbtc_combine_dec_verified_dev,
+                                           "hbtc_combine_dec_verified_dev", 48, counts, idx, shares,
+                                           status, t, False)
+        return g, cst
+
     def threshold_decrypt(self, keyset, H, w, counts, idx, shares, t, vs, offsets=None):
         """One ThresholdDecryption round (hbtc.h hbtc_threshold_decrypt): every share verified, the
         first t ACCEPTed shares of each ciphertext combined, and the plaintext v XOR hash_bytes(g)

@@ -287,6 +287,9 @@ __global__ void __launch_bounds__(256) k_fact_fill(uint32_t n, const Fr* __restr
   inv_fact[i] = inv;
 }
 
+// The M > n_fact bound below cannot be met by a call: the kernel runs for t <= LG_FACT_TMAX only
+// and leaves M - t > LG_FACT_RMAX, so the largest table entry ever read is 4096 + 256 = 4352 of the
+// n_fact = 65535 the context builds.  It guards the tables against other constants.
 constexpr uint32_t LG_FACT_RMAX = 256;
 constexpr uint32_t LG_FACT_TMAX = 4096;
 __global__ void __launch_bounds__(256) k_lagrange_fact(uint32_t t, const uint32_t* __restrict__ sel_idx,
