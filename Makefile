@@ -36,6 +36,8 @@ gen-fips:
 	python3 tools/gen_fips_asm.py > $(CSRC)/fq_fips_asm.h
 	python3 tools/gen_fips_asm.py --sr > $(CSRC)/fq_fips_sr.h
 	python3 tools/gen_fq_rr.py --selftest-rr
+	python3 tools/gen_fq_rr.py --selftest-w
+	python3 tools/rr_bounds.py
 	python3 tools/gen_fq_rr.py > $(CSRC)/fq_rr.h
 
 $(BUILD):
@@ -180,7 +182,7 @@ resources-own:
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
           tests/native/libhbtc_own_hosttest.so tests/native/libhbtc_msm_hosttest.so \
-          tests/native/libhbtc_rr_hosttest.so
+          tests/native/libhbtc_rr_hosttest.so tests/native/libhbtc_rrw_hosttest.so
 # the 13 x 30 Fq code's host build (field.h FqR over fq_rr.h's plain 64-bit schedule, every MAD
 # checked for a carry-out) and the G1 decode with its square root on it
 tests/native/libhbtc_rr_hosttest.so: tests/native/hbtc_rr_hosttest.cpp tests/native/hbtc_rr_ops.h $(HDRS)
@@ -191,6 +193,17 @@ sanitize-rr: | $(BUILD)
 	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
 	  tests/native/hbtc_rr_host_main.cpp tests/native/hbtc_rr_hosttest.cpp -o $(BUILD)/rr_host_asan
 	$(BUILD)/rr_host_asan
+# the redundant 13 x 30 form's host build (field.h FqW, curve.h jacw_*: the |x| chains of
+# k_rlc_decode's subgroup test), both bounds of every value tracked and asserted at every operation
+tests/native/libhbtc_rrw_hosttest.so: tests/native/hbtc_rrw_hosttest.cpp tests/native/hbtc_rrw_ops.h $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_rrw_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+# (RRW_TABLE=file runs the case table tests/rrw_cases.py wrote and prints every result)
+.PHONY: sanitize-rrw
+sanitize-rrw: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_rrw_host_main.cpp tests/native/hbtc_rrw_hosttest.cpp -o $(BUILD)/rrw_host_asan
+	$(BUILD)/rrw_host_asan $(RRW_TABLE)
 # msm_walk.h's host build (one wave of the lane-uniform bucket walk in lockstep, over a toy group
 # and over G1)
 tests/native/libhbtc_msm_hosttest.so: tests/native/hbtc_msm_hosttest.cpp $(HDRS)
@@ -255,7 +268,15 @@ $(BUILD)/hbtc_devtest.inl.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
 $(BUILD)/hbtc_devtest.call.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-devtest: tests/native/libhbtc_devtest.so tests/native/libhbtc_tree_devtest.so tests/native/libhbtc_rr_devtest.so
+devtest: tests/native/libhbtc_devtest.so tests/native/libhbtc_tree_devtest.so tests/native/libhbtc_rr_devtest.so \
+         tests/native/libhbtc_rrw_devtest.so
+# test-only device harness of the redundant 13 x 30 form (tests/test_gpu_rrw.py): the operations of
+# hbtc_rrw_ops.h on one workgroup, with the flags of hbtc_rlc.p6.o
+$(BUILD)/rr_devtest/hbtc_rrw_devtest.o: tests/native/hbtc_rrw_devtest.hip tests/native/hbtc_rrw_ops.h $(HDRS) | $(BUILD)
+	mkdir -p $(BUILD)/rr_devtest
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
+tests/native/libhbtc_rrw_devtest.so: $(BUILD)/rr_devtest/hbtc_rrw_devtest.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 # test-only device harness of the 13 x 30 Fq code (tests/test_gpu_rr.py): the operations of
 # hbtc_rr_ops.h on one workgroup, with the flags of hbtc_rlc.p6.o; the object stays out of
 # $(BUILD)/*.o, which tools/build_variant.sh links

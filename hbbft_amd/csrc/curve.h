@@ -1148,6 +1148,237 @@ HDN bool g1_in_subgroup(const G1A& p) {
   return jac_eq_aff(t2, bx, ny);
 }
 
+// ------------------------------------------- G1 on the redundant 13 x 30 form (field.h FqW)
+// The formulas and special cases of jac_dbl / jac_add_aff / jac_add / jac_eq_aff above, specialised:
+// every variable has its own bound, so the weak normalisations and the subtraction constants stand
+// at fixed places.  tools/rr_bounds.py holds the same schedules and shows, by pushing bounds through
+// them, that no limb wraps, every product operand is inside the relaxed blocks' bound, every
+// constant dominates its subtrahend, and every coordinate that leaves a formula -- on every exit --
+// is weakly normalised and at most 12 p again (the loop invariant of jacw_mul_x*).  Zero tests see
+// every representative of 0: they test a product result below 2p (Z^2, H^2, or r R' / R').
+struct AffW {
+  FqW x, y;  // never infinity
+};
+struct JacW {
+  FqW x, y, z;
+};
+HD void jacw_set_inf(JacW& r) {
+  fw_one(r.x);
+  fw_one(r.y);
+  fw_zero(r.z);
+}
+HD void affw_from_aff(AffW& r, const G1A& a) {
+  fw_from_fq(r.x, a.x);
+  fw_from_fq(r.y, a.y);
+}
+HD void jacw_to_jac(G1J& r, const JacW& p) {
+  fw_to_fq(r.x, p.x);
+  fw_to_fq(r.y, p.y);
+  fw_to_fq(r.z, p.z);  // 0 mod p stays 0 mod p: infinity is kept
+}
+HD bool jacw_is_inf(const JacW& p) {
+  FqW zz;
+  fw_sqr(zz, p.z);
+  return fw_is_zero(zz);
+}
+// dbl-2009-l (a = 0).  D = 2((X + B)^2 - A - C) = 4 X B is taken as the product X (4B): a product
+// result, which keeps X3 and Y3 at a few p; as a difference it is ~8 p, four times that in X3, and
+// the invariant does not close.  Z3 = 2 Y Z: Z = 0 mod p stays 0 mod p.
+HD void jacw_dbl(JacW& r, const JacW& p) {
+  FqW A, B, C, D, E, Fv, t, x3, y3, z3;
+  fw_mul(z3, p.y, p.z);
+  fw_dbl(z3, z3);
+  fw_norm(z3, z3);
+  fw_sqr(A, p.x);
+  fw_sqr(B, p.y);
+  fw_sqr(C, B);
+  fw_dbl(t, B);
+  fw_dbl(t, t);
+  fw_norm(t, t);  // 4B
+  fw_mul(D, p.x, t);
+  fw_dbl(E, A);
+  fw_add(E, E, A);
+  fw_norm(E, E);
+  fw_sqr(Fv, E);
+  fw_dbl(t, D);
+  fw_sub(x3, Fv, t, rr::RR_SUB_2_4, 4);
+  fw_norm(x3, x3);
+  fw_sub(t, D, x3, rr::RR_SUB_2_8, 8);
+  fw_norm(t, t);
+  fw_mul(y3, E, t);
+  fw_dbl(C, C);
+  fw_dbl(C, C);
+  fw_norm(C, C);  // 4C
+  fw_dbl(C, C);
+  fw_sub(y3, y3, C, rr::RR_SUB_2_10, 10);
+  fw_norm(y3, y3);
+  r.x = x3;
+  r.y = y3;
+  r.z = z3;
+}
+// the common second half of madd-2007-bl and add-2007-bl: x1 = U1 (or X1), s1 = S1 (or Y1)
+HD void jacw_add_tail(JacW& r, const FqW& x1, const FqW& s1, const FqW& H, const FqW& HH, const FqW& rr0,
+                      const FqW& z3) {
+  FqW I, J, r2, V, t, x3, y3;
+  fw_dbl(I, HH);
+  fw_dbl(I, I);
+  fw_norm(I, I);
+  fw_mul(J, H, I);
+  fw_dbl(r2, rr0);
+  fw_norm(r2, r2);
+  fw_mul(V, x1, I);
+  fw_sqr(x3, r2);
+  fw_sub(x3, x3, J, rr::RR_SUB_1_4, 4);
+  fw_norm(x3, x3);
+  fw_dbl(t, V);
+  fw_sub(x3, x3, t, rr::RR_SUB_2_4, 4);
+  fw_norm(x3, x3);
+  fw_sub(t, V, x3, rr::RR_SUB_2_14, 14);
+  fw_norm(t, t);
+  fw_mul(y3, r2, t);
+  fw_mul(t, s1, J);
+  fw_dbl(t, t);
+  fw_sub(y3, y3, t, rr::RR_SUB_2_4, 4);
+  fw_norm(y3, y3);
+  r.x = x3;
+  r.y = y3;
+  r.z = z3;
+}
+// madd-2007-bl: r = p + q
+HD void jacw_add_aff(JacW& r, const JacW& p, const AffW& q) {
+  FqW z1z1, u2, s2, H, HH, rr0, t, z3;
+  fw_sqr(z1z1, p.z);
+  if (fw_is_zero(z1z1)) {
+    r.x = q.x;
+    r.y = q.y;
+    fw_one(r.z);
+    return;
+  }
+  fw_mul(u2, q.x, z1z1);
+  fw_mul(s2, q.y, p.z);
+  fw_mul(s2, s2, z1z1);
+  fw_sub(H, u2, p.x, rr::RR_SUB_2_14, 14);
+  fw_norm(H, H);
+  fw_sub(rr0, s2, p.y, rr::RR_SUB_2_14, 14);
+  fw_norm(rr0, rr0);
+  fw_sqr(HH, H);
+  if (fw_is_zero(HH)) {
+    fw_one(t);
+    fw_mul(t, rr0, t);
+    if (fw_is_zero(t)) {
+      jacw_dbl(r, p);
+    } else {
+      jacw_set_inf(r);
+    }
+    return;
+  }
+  fw_add(t, p.z, H);
+  fw_norm(t, t);
+  fw_sqr(z3, t);
+  fw_add(t, z1z1, HH);
+  fw_sub(z3, z3, t, rr::RR_SUB_2_4, 4);
+  fw_norm(z3, z3);
+  jacw_add_tail(r, p.x, p.y, H, HH, rr0, z3);
+}
+// add-2007-bl: r = p + q
+HD void jacw_add(JacW& r, const JacW& p, const JacW& q) {
+  FqW z1z1, z2z2, u1, u2, s1, s2, H, HH, rr0, t, z3;
+  fw_sqr(z1z1, p.z);
+  if (fw_is_zero(z1z1)) {
+    r = q;
+    return;
+  }
+  fw_sqr(z2z2, q.z);
+  if (fw_is_zero(z2z2)) {
+    r = p;
+    return;
+  }
+  fw_mul(u1, p.x, z2z2);
+  fw_mul(u2, q.x, z1z1);
+  fw_mul(s1, p.y, q.z);
+  fw_mul(s1, s1, z2z2);
+  fw_mul(s2, q.y, p.z);
+  fw_mul(s2, s2, z1z1);
+  fw_sub(H, u2, u1, rr::RR_SUB_1_4, 4);
+  fw_norm(H, H);
+  fw_sub(rr0, s2, s1, rr::RR_SUB_1_4, 4);
+  fw_norm(rr0, rr0);
+  fw_sqr(HH, H);
+  if (fw_is_zero(HH)) {
+    fw_one(t);
+    fw_mul(t, rr0, t);
+    if (fw_is_zero(t)) {
+      jacw_dbl(r, p);
+    } else {
+      jacw_set_inf(r);
+    }
+    return;
+  }
+  fw_add(t, p.z, q.z);
+  fw_norm(t, t);
+  fw_sqr(z3, t);
+  fw_add(t, z1z1, z2z2);
+  fw_sub(z3, z3, t, rr::RR_SUB_2_4, 4);
+  fw_norm(z3, z3);
+  fw_mul(z3, z3, H);
+  jacw_add_tail(r, u1, s1, H, HH, rr0, z3);
+}
+// Is p (not infinity) the affine point (ax, ay)?  Both sides as product results, compared as
+// canonical residues.  ax, ay weakly normalised.
+HD bool jacw_eq_aff(const JacW& p, const FqW& ax, const FqW& ay) {
+  FqW z2, z3, t, u, one;
+  fw_one(one);
+  fw_sqr(z2, p.z);
+  fw_mul(z3, z2, p.z);
+  fw_mul(t, ax, z2);
+  fw_mul(u, p.x, one);
+  if (!fw_eq(t, u)) return false;
+  fw_mul(t, ay, z3);
+  fw_mul(u, p.y, one);
+  return fw_eq(t, u);
+}
+// [|x|] q: jac_mul_u64(.., BLS_X_ABS) and jac_mul_u64_jac(.., BLS_X_ABS) on this form
+HDN void jacw_mul_x(JacW& r, const AffW& q) {
+  JacW acc;
+  jacw_set_inf(acc);
+  for (int b = 63; b >= 0; --b) {
+    jacw_dbl(acc, acc);
+    if ((BLS_X_ABS >> b) & 1ull) jacw_add_aff(acc, acc, q);
+  }
+  r = acc;
+}
+HDN void jacw_mul_x_jac(JacW& r, const JacW& q) {
+  JacW acc;
+  jacw_set_inf(acc);
+  for (int b = 63; b >= 0; --b) {
+    jacw_dbl(acc, acc);
+    if ((BLS_X_ABS >> b) & 1ull) jacw_add(acc, acc, q);
+  }
+  r = acc;
+}
+// g1_in_subgroup_t1 with both chains on the redundant form: t = [|x|] p in 12 x 32 Montgomery (a
+// congruent Jacobian representative of the 12 x 32 chain's), the verdict the same
+HDN bool g1_in_subgroup_t1_w(const G1A& p, G1J& t) {
+  if (p.inf) {
+    jac_set_inf(t);
+    return true;
+  }
+  AffW q;
+  affw_from_aff(q, p);
+  JacW t1, t2;
+  jacw_mul_x(t1, q);
+  jacw_to_jac(t, t1);
+  jacw_mul_x_jac(t2, t1);  // [x^2] P
+  if (jacw_is_inf(t2)) return false;
+  FqW beta, bx, ny;
+  Fq fb;
+  fq_set(fb, G1_BETA);
+  fw_from_fq(beta, fb);
+  fw_mul(bx, q.x, beta);
+  fw_neg(ny, q.y);  // phi(P) == -[x^2]P  <=>  (beta x, -y) == [x^2] P
+  return jacw_eq_aff(t2, bx, ny);
+}
+
 HD void g2_psi(Fq2& rx, Fq2& ry, const G2A& p) {
   Fq2 c, k;
   fq2_conj(c, p.x);

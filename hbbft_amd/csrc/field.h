@@ -71,10 +71,11 @@
 #include "fq_fips_sr.h"
 #endif
 // The product and squaring on 13 limbs of 30 bits (tools/gen_fq_rr.py): no carry word per MAC.
-// HBTC_FQ_RR=1 runs the square root of k_rlc_decode's G1 decode on it (FqR below); 0 builds the
-// 12 x 32 code everywhere, for comparisons.
+// HBTC_FQ_RR=1 runs the square root of k_rlc_decode's G1 decode on it (FqR below); 2 also runs the
+// two |x| chains of that kernel's subgroup test on its redundant form (FqW below, curve.h jacw_*);
+// 0 builds the 12 x 32 code everywhere, for comparisons.
 #ifndef HBTC_FQ_RR
-#define HBTC_FQ_RR 1
+#define HBTC_FQ_RR 2
 #endif
 #include "fq_rr.h"
 
@@ -785,7 +786,215 @@ HD bool fq_sqrt_rr(Fq& r, const Fq& a) {
   return fqr_eq(y2, ar);
 }
 
-// canonical(a) > (p-1)/2   <=>  a > -a  (pairing 0.14 ordering on canonical values, a != 0)
+// ------------------------------------------- the redundant form of the 13 x 30 code (HBTC_FQ_RR=2)
+// FqW holds a R' mod p like FqR, but sums and differences are taken limb by limb with no carry and
+// no reduction: limbs may pass 2^30 - 1 and the value may pass p by a multiple that
+// tools/rr_bounds.py tracks through every formula that uses the type (curve.h jacw_*).
+//   fw_add / fw_dbl   13 independent adds
+//   fw_sub            a + C - s, C a multiple of p spelled so that each limb dominates the limb of
+//                     s below it (fq_rr.h RR_SUB_b_k: k p with b units of 2^30 lent to every limb)
+//   fw_norm           one parallel round l_i = (l_i & mask) + (l_(i-1) >> 30): limbs <= 2^30 + 2
+//                     again, the top limb keeps its high bits and is bounded by the value
+//   fw_mul / fw_sqr   the relaxed-bound blocks: weakly normalised operands up to 64 p, the result
+//                     on limbs < 2^30 and below (A B / 630 + 1) p
+//   fw_is_zero        of a product result below 2p: it is 0 or p
+// The host build under HBTC_RR_ASSERT carries both bounds beside every value and checks them, and
+// the claims above, at every operation (the product's plain C++ schedule checks every MAD).
+#if defined(HBTC_RR_ASSERT) && !defined(__HIPCC__)
+#define HBTC_FW_TRACK 1
+#else
+#define HBTC_FW_TRACK 0
+#endif
+struct FqW {
+  uint32_t v[13];
+#if HBTC_FW_TRACK
+  uint64_t lb[13];  // per-limb maxima
+  uint64_t vb;      // value maximum in units of p / 2^16
+#endif
+};
+#if HBTC_FW_TRACK
+HBTC_CONST uint64_t FW_ONE_P = 1ull << 16;
+static inline void fw_fail(const char* what) {
+  std::fprintf(stderr, "FqW bound violated: %s\n", what);
+  std::abort();
+}
+// the top limb of a value <= vb: p < (RR_P[12] + 1) 2^360 and every limb is non-negative
+static inline uint64_t fw_top_of(uint64_t vb) { return (vb * ((uint64_t)rr::RR_P[12] + 1)) >> 16; }
+static inline void fw_set_bounds(FqW& r, const uint64_t* lb, uint64_t vb) {
+  for (int i = 0; i < 13; ++i) r.lb[i] = lb[i];
+  r.vb = vb;
+  if (fw_top_of(vb) < r.lb[12]) r.lb[12] = fw_top_of(vb);
+  for (int i = 0; i < 13; ++i) {
+    if (r.lb[i] > 0xffffffffull) fw_fail("a limb may wrap");
+    if (r.v[i] > r.lb[i]) fw_fail("a limb above its tracked bound");
+  }
+}
+static inline void fw_set_strict(FqW& r, uint64_t vb) {
+  uint64_t lb[13];
+  for (int i = 0; i < 13; ++i) lb[i] = rr::RR_MASK;
+  fw_set_bounds(r, lb, vb);
+}
+static inline void fw_check_operand(const FqW& a) {
+  for (int i = 0; i < 13; ++i)
+    if (a.lb[i] > (i < 12 ? (uint64_t)rr::RR_MASK + rr::RR_W_SLACK : (uint64_t)rr::RR_W_TOP))
+      fw_fail("a product operand outside the relaxed blocks' bound");
+}
+static inline uint64_t fw_prod_vb(uint64_t va, uint64_t vb) {  // (A B / 630 + 1) p, rounded up
+  return (va * vb + 630ull * FW_ONE_P - 1) / (630ull * FW_ONE_P) + FW_ONE_P;
+}
+#endif
+HD void fw_add(FqW& r, const FqW& a, const FqW& b) {
+#if HBTC_FW_TRACK
+  uint64_t lb[13];
+  for (int i = 0; i < 13; ++i) lb[i] = a.lb[i] + b.lb[i];
+  const uint64_t vb = a.vb + b.vb;
+#endif
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = a.v[i] + b.v[i];
+#if HBTC_FW_TRACK
+  fw_set_bounds(r, lb, vb);
+#endif
+}
+HD void fw_dbl(FqW& r, const FqW& a) { fw_add(r, a, a); }
+// r = a + C - s for C = k p (RR_SUB_b_k)
+HD void fw_sub(FqW& r, const FqW& a, const FqW& s, const uint32_t (&C)[13], uint32_t k) {
+#if HBTC_FW_TRACK
+  uint64_t lb[13];
+  for (int i = 0; i < 13; ++i) {
+    if (C[i] < s.lb[i]) fw_fail("a subtraction constant below its subtrahend's bound");
+    lb[i] = a.lb[i] + C[i];
+  }
+  const uint64_t vb = a.vb + k * FW_ONE_P;
+#endif
+  (void)k;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = a.v[i] + (C[i] - s.v[i]);
+#if HBTC_FW_TRACK
+  fw_set_bounds(r, lb, vb);
+#endif
+}
+HD void fw_norm(FqW& r, const FqW& a) {
+  uint32_t t[13];
+  t[0] = a.v[0] & rr::RR_MASK;
+#pragma unroll
+  for (int i = 1; i < 12; ++i) t[i] = (a.v[i] & rr::RR_MASK) + (a.v[i - 1] >> 30);
+  t[12] = a.v[12] + (a.v[11] >> 30);
+#if HBTC_FW_TRACK
+  uint64_t lb[13];
+  lb[0] = rr::RR_MASK;
+  for (int i = 1; i < 12; ++i) lb[i] = rr::RR_MASK + (a.lb[i - 1] >> 30);
+  lb[12] = a.lb[12] + (a.lb[11] >> 30);
+  const uint64_t vb = a.vb;
+#endif
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = t[i];
+#if HBTC_FW_TRACK
+  fw_set_bounds(r, lb, vb);
+#endif
+}
+HD void fw_mul(FqW& r, const FqW& a, const FqW& b) {
+#if HBTC_FW_TRACK
+  fw_check_operand(a);
+  fw_check_operand(b);
+  const uint64_t vb = fw_prod_vb(a.vb, b.vb);
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+  rr::mont_mul_w_asm(r.v, a.v, b.v);
+#else
+  rr::mont_mul_w_cxx(r.v, a.v, b.v);
+#endif
+#if HBTC_FW_TRACK
+  fw_set_strict(r, vb);
+#endif
+}
+HD void fw_sqr(FqW& r, const FqW& a) {
+#if HBTC_FW_TRACK
+  fw_check_operand(a);
+  const uint64_t vb = fw_prod_vb(a.vb, a.vb);
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+  rr::mont_sqr_w_asm(r.v, a.v);
+#else
+  rr::mont_sqr_w_cxx(r.v, a.v);
+#endif
+#if HBTC_FW_TRACK
+  fw_set_strict(r, vb);
+#endif
+}
+HD void fw_set(FqW& r, const uint32_t (&c)[13]) {  // a constant below p on limbs < 2^30
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = c[i];
+#if HBTC_FW_TRACK
+  fw_set_strict(r, FW_ONE_P);
+#endif
+}
+HD void fw_one(FqW& r) { fw_set(r, rr::RR_ONE); }
+HD void fw_zero(FqW& r) {
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = 0;
+#if HBTC_FW_TRACK
+  uint64_t lb[13] = {0};
+  fw_set_bounds(r, lb, 0);
+#endif
+}
+// r = -a (a product result or a constant: limbs < 2^30, below 3p), weakly normalised, <= 4p
+HD void fw_neg(FqW& r, const FqW& a) {
+  FqW z;
+  fw_zero(z);
+  fw_sub(r, z, a, rr::RR_SUB_1_4, 4);
+  fw_norm(r, r);
+}
+// Is a == 0 mod p?  For a product result below 2p only: such a value is 0 mod p exactly when it is
+// 0 or p.  Callers test the square the formulas compute anyway (Z^2, H^2), or one product by R'.
+HD bool fw_is_zero(const FqW& a) {
+#if HBTC_FW_TRACK
+  for (int i = 0; i < 12; ++i)
+    if (a.lb[i] > rr::RR_MASK) fw_fail("zero test on limbs above 2^30 - 1");
+  if (a.vb >= 2 * FW_ONE_P) fw_fail("zero test on a value that may reach 2p");
+#endif
+  uint32_t z = 0, d = 0;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    z |= a.v[i];
+    d |= a.v[i] ^ rr::RR_P[i];
+  }
+  return z == 0 || d == 0;
+}
+// a == b mod p for two product results below 2p, as canonical residues (fqr_canon)
+HD bool fw_eq(const FqW& a, const FqW& b) {
+#if HBTC_FW_TRACK
+  for (int i = 0; i < 12; ++i)
+    if (a.lb[i] > rr::RR_MASK || b.lb[i] > rr::RR_MASK) fw_fail("comparison on limbs above 2^30 - 1");
+  if (a.vb >= 2 * FW_ONE_P || b.vb >= 2 * FW_ONE_P) fw_fail("comparison of a value that may reach 2p");
+#endif
+  FqR x, y;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    x.v[i] = a.v[i];
+    y.v[i] = b.v[i];
+  }
+  return fqr_eq(x, y);
+}
+HD void fw_from_fq(FqW& r, const Fq& a) {  // a R (< 2p) -> a R', a product result < 1.5p
+  FqR t;
+  fqr_from_fq(t, a);
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = t.v[i];
+#if HBTC_FW_TRACK
+  fw_set_strict(r, FW_ONE_P + FW_ONE_P / 2);
+#endif
+}
+HD void fw_to_fq(Fq& r, const FqW& a) {  // a R' (weakly normalised, <= 64p) -> a R (< 2p)
+  FqW k, t;
+  fw_set(k, rr::RR_K_OUT);
+  fw_mul(t, a, k);
+  FqR u;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) u.v[i] = t.v[i];
+  fqr_limbs32(r, u);
+}
+
+// canonical(a) > (p-1)/2  <=>  a > -a  (pairing 0.14 ordering on canonical values, a != 0)
 HD bool fq_is_lex_largest(const Fq& a) {
   Fq c;
   fq_from_mont(c, a);

@@ -131,6 +131,38 @@ __global__ void __launch_bounds__(64, HBTC_RLC_DEC_WAVES) k_rlc_decode(
       // comparison, so the second multiplication runs with only t1 live beside its accumulator
       // (332 -> 192 B/lane of scratch at three waves per SIMD)
       dec[item] = d;
+#if HBTC_FQ_RR >= 2
+      // both chains on the redundant 13 x 30 form (curve.h jacw_*): d goes into it once, t1 comes out
+      // to 12 x 32 Montgomery for t1s (a congruent Jacobian representative of the 12 x 32 chain's; the
+      // layout and every reader are unchanged) and stays, 13-limb, the second chain's base; the final
+      // comparison runs in the same form against the re-read d
+      JacW t1, t2;
+      {
+        AffW q;
+        affw_from_aff(q, d);
+        jacw_mul_x(t1, q);
+      }
+      {
+        G1J t1o;
+        jacw_to_jac(t1o, t1);
+        t1s[item] = t1o;
+      }
+      jacw_mul_x_jac(t2, t1);             // [x^2] d
+      __asm__ volatile("" ::: "memory");  // d is re-read, not kept in registers
+      const G1A dd = dec[item];
+      FqW bx, ny;
+      {
+        Fq fb;
+        FqW beta, x, y;
+        fq_set(fb, G1_BETA);
+        fw_from_fq(beta, fb);
+        fw_from_fq(x, dd.x);
+        fw_from_fq(y, dd.y);
+        fw_mul(bx, x, beta);
+        fw_neg(ny, y);  // phi(d) == -[x^2] d  <=>  (beta x, -y) == [x^2] d
+      }
+      if (jacw_is_inf(t2) || !jacw_eq_aff(t2, bx, ny)) st = HBTC_DECODE_ERR;
+#else
       G1J t1, t2;
       jac_mul_u64(t1, d, BLS_X_ABS);
       t1s[item] = t1;
@@ -142,6 +174,7 @@ __global__ void __launch_bounds__(64, HBTC_RLC_DEC_WAVES) k_rlc_decode(
       fq_mul(bx, dd.x, beta);
       fq_neg(ny, dd.y);  // phi(d) == -[x^2] d  <=>  (beta x, -y) == [x^2] d
       if (jac_is_inf(t2) || !jac_eq_aff(t2, bx, ny)) st = HBTC_DECODE_ERR;
+#endif
     } else {
       G1J t1;
       jac_set_inf(t1);

@@ -28,7 +28,13 @@ its top limb may then pass 2^30.
 Squaring: sum_i a_i^2 + sum_(i<j) a_i (2 a_j), the doubled limbs d_j = 2 a_j < 2^31 formed outside
 the block: 91 + 169 MADs against the product's 169 + 169.
 
-Usage: tools/gen_fq_rr.py > hbbft_amd/csrc/fq_rr.h ; tools/gen_fq_rr.py --selftest-rr
+Operand bounds are a parameter, per limb (schedule(square, la, lb)): the default, every limb
+<= 2^30 - 1, gives mont_mul / mont_sqr; the weakly normalised operands of the redundant form (W_LIMBS
+below: limbs 0..11 <= 2^30 + 2, the top limb bounded by the value) give mont_mul_w / mont_sqr_w, whose
+splits stand elsewhere.  The subtraction constants of that form (sub_const) are emitted here too.
+
+Usage: tools/gen_fq_rr.py > hbbft_amd/csrc/fq_rr.h ; tools/gen_fq_rr.py --selftest-rr ;
+tools/gen_fq_rr.py --selftest-w
 """
 import random
 import sys
@@ -48,15 +54,47 @@ def limbs(v):
     return [(v >> (W * i)) & M for i in range(N)]
 
 
-def schedule(square):
+# ---- the redundant form (field.h FqW): sums and differences are taken limb by limb with no carry,
+# so limbs pass 2^30 - 1 and the value passes p by a tracked multiple.  One weak normalisation
+# l_i = (l_i & M) + (l_(i-1) >> 30) of limbs below 2^32 leaves limbs <= M + W_SLACK (the top limb
+# keeps its high bits and is bounded by the value alone).  The relaxed blocks (mont_mul_w,
+# mont_sqr_w) take such operands with values up to W_VMAX p; their result has limbs <= M again and
+# is below (A B / 630 + 1) p for operands <= A p, B p (2^390 / p = 630.07).
+W_SLACK = 3
+W_VMAX = 64
+W_LIMBS = [M + W_SLACK] * (N - 1) + [(W_VMAX * P_MOD) >> (W * (N - 1))]
+ONE = (1 << RBITS) % P_MOD                                     # the Montgomery one, R' mod p
+
+
+def sub_const(b, k):
+    """k p spelled with b units of 2^30 borrowed from every limb above into the limb below: every
+    limb but the top is at least b (2^30 - 1), so a + sub_const - s has no borrow for a subtrahend
+    whose limbs the constant dominates (tools/rr_bounds.py checks each use limb by limb)."""
+    assert k * P_MOD < 1 << RBITS
+    l = limbs(k * P_MOD)
+    c = [l[0] + (b << W)] + [l[i] + (b << W) - b for i in range(1, N - 1)] + [l[N - 1] - b]
+    assert all(0 <= x < 1 << 32 for x in c) and sum(x << (W * i) for i, x in enumerate(c)) == k * P_MOD
+    return c
+
+
+# the constants the point formulas of curve.h use: (units borrowed, multiple of p), one per bound
+# class of subtrahend (strict limbs and a small value; twice a strict or normalised value, ...)
+SUB_CONSTS = [(1, 4), (2, 4), (2, 8), (2, 10), (2, 14)]
+
+
+def schedule(square, la=None, lb=None):
     """The instruction list in symbolic form, with the overflow splits the bounds require.
+    la, lb: the operands' per-limb maxima (13 each; default every limb 2^30 - 1; a squaring takes la).
     Ops: ("mad", x, y) acc += x y; ("mad0", x, y) acc = x y; ("madh",) acc += 4 h;
     ("split32",) h = acc.hi, acc.hi = 0; ("q", k) q_k = (acc.lo n') & M; ("out", j) r_j = acc.lo & M;
     ("carry",) the other pair = acc >> 30 and becomes acc; ("top",) r_12 = acc >> 30."""
+    la = la or [M] * N
+    lb = la if square else (lb or [M] * N)
     lim = {}
     for i in range(N):
-        lim["a%d" % i] = lim["b%d" % i] = lim["q%d" % i] = M
-        lim["d%d" % i] = 2 * M
+        lim["a%d" % i], lim["b%d" % i], lim["q%d" % i] = la[i], lb[i], M
+        lim["d%d" % i] = 2 * la[i]
+        assert lim["d%d" % i] < 1 << 32, "a doubled limb of the squaring passes 32 bits"
         lim["p%d" % i] = P_L[i]
     ops, info = [], {"splits": [], "max": 0}
     bound, hb, h_live = 0, 0, False   # accumulator bound, bound of h, h pending for this column
@@ -208,8 +246,8 @@ def asm_lines(ops, square):
     return out
 
 
-def asm_block(name, square):
-    ops, _ = schedule(square)
+def asm_block(name, square, la=None, lb=None):
+    ops, _ = schedule(square, la, lb)
     text = "\n".join('      "%s\\n\\t"' % l for l in asm_lines(ops, square))
     outs = ", ".join('"=&v"(r[%d])' % i for i in range(N)) + ",\n        " + \
         ", ".join('"=&v"(q[%d])' % i for i in range(N)) + ', "=&v"(h)'
@@ -238,10 +276,10 @@ def asm_block(name, square):
 """ % (name, args, prep, text, outs, ins, clob)
 
 
-def cxx_block(name, square):
+def cxx_block(name, square, la=None, lb=None):
     """The same schedule as straight-line C++ on one 64-bit accumulator.  HBTC_RR_MAD checks the
     no-carry-out claim when HBTC_RR_ASSERT is defined (host tests)."""
-    ops, _ = schedule(square)
+    ops, _ = schedule(square, la, lb)
     v = lambda s: "%s[%s]" % (s[0], s[1:])
     body = []
     for op in ops:
@@ -331,6 +369,27 @@ namespace rr {
 """)
     print(asm_block("mont_mul_asm", False))
     print(asm_block("mont_sqr_asm", True))
+    _, wm = schedule(False, W_LIMBS, W_LIMBS)
+    _, wsq = schedule(True, W_LIMBS)
+    print("""#endif
+
+// ---- the relaxed-bound blocks of the redundant form (field.h FqW): operands weakly normalised,
+// limbs 0..11 <= 2^30 - 1 + %d and the top limb <= 0x%x (values up to %d p); the result has limbs
+// <= 2^30 - 1 and is below (A B / 630 + 1) p for operands <= A p and B p.  Overflow splits in
+// columns %s (product) and %s (squaring).
+HBTC_RR_CONST uint32_t RR_W_SLACK = %du;
+HBTC_RR_CONST uint32_t RR_W_TOP = 0x%08xu;""" % (W_SLACK, W_LIMBS[N - 1], W_VMAX, wm["splits"], wsq["splits"],
+                                                   W_SLACK, W_LIMBS[N - 1]))
+    print(arr("RR_ONE", limbs(ONE)) + "  // 2^390 mod p: the Montgomery one")
+    for b, k in SUB_CONSTS:
+        print(arr("RR_SUB_%d_%d" % (b, k), sub_const(b, k)) +
+              "  // %d p with %d borrowed per limb: a + this - s for limbs of s <= these" % (k, b))
+    print()
+    print(cxx_block("mont_mul_w_cxx", False, W_LIMBS, W_LIMBS))
+    print(cxx_block("mont_sqr_w_cxx", True, W_LIMBS))
+    print("#if defined(__HIP_DEVICE_COMPILE__)")
+    print(asm_block("mont_mul_w_asm", False, W_LIMBS, W_LIMBS))
+    print(asm_block("mont_sqr_w_asm", True, W_LIMBS))
     print("""#endif
 }  // namespace rr
 }  // namespace hbtc""")
@@ -378,10 +437,48 @@ def selftest_rr(trials=300):
     print("selftest_rr conversions ok")
 
 
+def selftest_w(trials=300):
+    """The relaxed-bound blocks on the simulator: operands spelled with limbs up to W_LIMBS (not
+    canonical: the value is what the limbs spell), no MAD carry-out, the result congruent to
+    a b / 2^390, its limbs 0..11 <= 2^30 - 1 and its value below a b / 2^390 + p."""
+    rng = random.Random(14)
+    Ri = pow(1 << RBITS, -1, P_MOD)
+    top = sum(x << (W * i) for i, x in enumerate(W_LIMBS))
+    edge = [limbs(v) for v in [0, 1, P_MOD - 1, P_MOD] + [k * P_MOD - 1 for k in range(2, W_VMAX + 1)]]
+    edge.append(list(W_LIMBS))                                  # every limb at its declared maximum
+    edge.append([M + W_SLACK] * (N - 1) + [0])
+    rnd = lambda: [rng.randrange(W_LIMBS[i] + 1) for i in range(N)]
+    pairs = [(x, y) for x in edge for y in edge] + [(rnd(), rnd()) for _ in range(trials)]
+    for square in (False, True):
+        ops, info = schedule(square, W_LIMBS, W_LIMBS)
+        assert info["max"] <= U64
+        for a, b in pairs:
+            if square:
+                b = a
+            assert all(x <= w for x, w in zip(a, W_LIMBS)) and all(x <= w for x, w in zip(b, W_LIMBS))
+            va = sum(x << (W * i) for i, x in enumerate(a))
+            vb = sum(x << (W * i) for i, x in enumerate(b))
+            assert va <= top and vb <= top
+            r = run(ops, a, None if square else b)
+            val = sum(x << (W * i) for i, x in enumerate(r))
+            assert val % P_MOD == va * vb * Ri % P_MOD, (square, a, b)
+            assert all(x <= M for x in r[:N - 1]) and val < (va * vb >> RBITS) + P_MOD + 1
+        mads = sum(op[0] in ("mad", "mad0", "madh") for op in ops)
+        print("selftest_w %s ok: %d MADs, splits in columns %s, %d instructions, largest column bound "
+              "2^64 - %d" % ("squaring" if square else "product", mads, info["splits"],
+                             len(asm_lines(ops, square)), U64 + 1 - info["max"]))
+    for b, k in SUB_CONSTS:
+        c = sub_const(b, k)
+        assert min(c[:N - 1]) >= b * M and c[N - 1] > 0
+    print("selftest_w constants ok")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--selftest-rr":
         selftest_rr()
+    elif len(sys.argv) > 1 and sys.argv[1] == "--selftest-w":
+        selftest_w()
     elif len(sys.argv) == 1:
         main()
     else:
-        sys.exit("usage: gen_fq_rr.py [--selftest-rr]")
+        sys.exit("usage: gen_fq_rr.py [--selftest-rr | --selftest-w]")

@@ -2,13 +2,16 @@
 // Variants: rolled CIOS (round-1 default), fully unrolled CIOS, and product-scanning (FIPS)
 // with the 64-bit multiply-add's carry-out feeding a 32-bit column-overflow counter
 // (grouped inline-asm MACs), and the carry-free 13 x 30 product / squaring of fq_rr.h against the
-// one-block 12 x 32 forms at 1 / 2 / 3 waves per SIMD.  Prints time, Fqm/s and the fraction of the measured
+// one-block 12 x 32 forms at 1 / 2 / 3 waves per SIMD, and one jac_dbl step on 12 x 32 (curve.h jac_dbl)
+// against the redundant 13 x 30 form (jacw_dbl) at the same occupancies (for this A/B build with
+// -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE, the flags of k_rlc_decode's object: the 12 x 32 doubling then
+// has its products inlined as in that kernel).  Prints time, Fqm/s and the fraction of the measured
 // v_mad_u64_u32 roofline (29.51e12 / 288 Fqm/s), plus a cross-check of the three results.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "field.h"
+#include "curve.h"
 #include "fq_fips.h"
 #include "fq_fips_asm.h"
 using namespace hbtc;
@@ -27,8 +30,13 @@ __device__ __forceinline__ void mulv(Fq& r, const Fq& a, const Fq& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   else if constexpr (V == 3) fips::mont_mul_asm(r.v, a.v, b.v);
   else if constexpr (V == 5) fips::mont_sqr_asm(r.v, a.v);
+#if defined(HBTC_FQMUL_SR)
   else if constexpr (V == 6) fips::mont_mul_sr(r.v, a.v, b.v);  // subroutine (fq_fips_sr.h)
   else fips::mont_sqr_sr(r.v, a.v);
+#else  // built with -DHBTC_FQMUL_INLINE (the flags of k_rlc_decode's object): 6 / 7 repeat 3 / 5
+  else if constexpr (V == 6) fips::mont_mul_asm(r.v, a.v, b.v);
+  else fips::mont_sqr_asm(r.v, a.v);
+#endif
 #endif
 }
 
@@ -83,6 +91,42 @@ __global__ void k_check_rr(const FqR* in, FqR* out) {
   out[i] = r;
 }
 
+// One G1 doubling per iteration: V 0 jac_dbl on 12 x 32 (in: three Fq), V 1 jacw_dbl on the redundant
+// 13 x 30 form (in: three entry-bound FqW: limbs < 2^30, below 2^384 < 12p).  N iterations.
+constexpr int DBL_ITERS = 128;
+template <int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_dbl12(const Fq* in, Fq* out, int n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  G1J p;
+  p.x = in[i & 1023];
+  p.y = in[(i + 1) & 1023];
+  p.z = in[(i + 2) & 1023];
+#pragma unroll 1
+  for (int it = 0; it < n; ++it) jac_dbl(p, p);
+  fq_canon(out[3 * (size_t)i], p.x);
+  fq_canon(out[3 * (size_t)i + 1], p.y);
+  fq_canon(out[3 * (size_t)i + 2], p.z);
+}
+template <int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_dblw(const FqR* in, FqR* out, int n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  JacW p;
+#pragma unroll
+  for (int l = 0; l < 13; ++l) {
+    p.x.v[l] = in[i & 1023].v[l];
+    p.y.v[l] = in[(i + 1) & 1023].v[l];
+    p.z.v[l] = in[(i + 2) & 1023].v[l];
+  }
+#pragma unroll 1
+  for (int it = 0; it < n; ++it) jacw_dbl(p, p);
+#pragma unroll
+  for (int l = 0; l < 13; ++l) {
+    out[3 * (size_t)i].v[l] = p.x.v[l];
+    out[3 * (size_t)i + 1].v[l] = p.y.v[l];
+    out[3 * (size_t)i + 2].v[l] = p.z.v[l];
+  }
+}
+
 template <int V>
 __global__ void k_check(const Fq* in, Fq* out) {
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -106,7 +150,7 @@ int main() {
   Fq *d_in, *d_out;
   const int nthreads = 256 * 2048;
   CHK(hipMalloc(&d_in, sizeof(Fq) * 1024));
-  CHK(hipMalloc(&d_out, sizeof(Fq) * nthreads));
+  CHK(hipMalloc(&d_out, sizeof(Fq) * 3 * nthreads));
   CHK(hipMemcpy(d_in, h.data(), sizeof(Fq) * 1024, hipMemcpyHostToDevice));
   // cross-check
   std::vector<Fq> rv[8];
@@ -146,7 +190,7 @@ int main() {
   }
   FqR *d_in13, *d_out13;
   CHK(hipMalloc(&d_in13, sizeof(FqR) * 1024));
-  CHK(hipMalloc(&d_out13, sizeof(FqR) * nthreads));
+  CHK(hipMalloc(&d_out13, sizeof(FqR) * 3 * nthreads));
   CHK(hipMemcpy(d_in13, hr13.data(), sizeof(FqR) * 1024, hipMemcpyHostToDevice));
   {
     std::vector<FqR> got(1024);
@@ -219,5 +263,64 @@ int main() {
   RUNW(k_mul_rr, 0, "A/B 13x30 product (fq_rr.h)", run13)
   RUNW(k_mul, 5, "A/B 12x32 squaring (one-block asm)", run)
   RUNW(k_mul_rr, 1, "A/B 13x30 squaring (fq_rr.h)", run13)
+  // one G1 doubling: 4 doublings cross-checked against the host build of the same functions (canonical
+  // limbs for 12 x 32; the redundant form bit for bit, its host product being the same schedule)
+  {
+    const int K = 4;
+    std::vector<Fq> g12(3 * 256);
+    std::vector<FqR> gw(3 * 256);
+    hipLaunchKernelGGL(k_dbl12<1>, dim3(1), dim3(256), 0, 0, d_in, d_out, K);
+    CHK(hipMemcpy(g12.data(), d_out, sizeof(Fq) * 3 * 256, hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(k_dblw<1>, dim3(1), dim3(256), 0, 0, d_in13, d_out13, K);
+    CHK(hipMemcpy(gw.data(), d_out13, sizeof(FqR) * 3 * 256, hipMemcpyDeviceToHost));
+    int bad12 = 0, badw = 0;
+    for (int i = 0; i < 256; ++i) {
+      G1J p;
+      p.x = h[i & 1023];
+      p.y = h[(i + 1) & 1023];
+      p.z = h[(i + 2) & 1023];
+      JacW q;
+      for (int l = 0; l < 13; ++l) {
+        q.x.v[l] = hr13[i & 1023].v[l];
+        q.y.v[l] = hr13[(i + 1) & 1023].v[l];
+        q.z.v[l] = hr13[(i + 2) & 1023].v[l];
+      }
+      for (int k = 0; k < K; ++k) {
+        jac_dbl(p, p);
+        jacw_dbl(q, q);
+      }
+      Fq c[3];
+      fq_canon(c[0], p.x);
+      fq_canon(c[1], p.y);
+      fq_canon(c[2], p.z);
+      const FqW* w[3] = {&q.x, &q.y, &q.z};
+      for (int j = 0; j < 3; ++j) {
+        for (int l = 0; l < 12; ++l) bad12 += g12[3 * i + j].v[l] != c[j].v[l];
+        for (int l = 0; l < 13; ++l) badw += gw[3 * i + j].v[l] != w[j]->v[l];
+      }
+    }
+    printf("cross-check jac_dbl vs host: 12x32 %s (%d limb mismatches), redundant 13x30 %s (%d)\n",
+           bad12 ? "FAIL" : "ok", bad12, badw ? "FAIL" : "ok", badw);
+  }
+  auto rund = [&](const char* name, auto launch, int blocks) {
+    launch(blocks);
+    CHK(hipDeviceSynchronize());
+    CHK(hipEventRecord(a));
+    launch(blocks);
+    CHK(hipEventRecord(b));
+    CHK(hipEventSynchronize(b));
+    float ms;
+    CHK(hipEventElapsedTime(&ms, a, b));
+    printf("%-40s blocks=%5d %8.3f ms %9.3e doublings/s\n", name, blocks, ms,
+           (double)blocks * 256 * DBL_ITERS / (ms * 1e-3));
+  };
+#define RUND(W)                                                                                              \
+  rund("A/B jac_dbl 12x32 " #W "w/SIMD",                                                                     \
+       [&](int bl) { hipLaunchKernelGGL(k_dbl12<W>, dim3(bl), dim3(256), 0, 0, d_in, d_out, DBL_ITERS); }, 256 * W); \
+  rund("A/B jacw_dbl 13x30 redundant " #W "w/SIMD",                                                          \
+       [&](int bl) { hipLaunchKernelGGL(k_dblw<W>, dim3(bl), dim3(256), 0, 0, d_in13, d_out13, DBL_ITERS); }, 256 * W);
+  RUND(1)
+  RUND(2)
+  RUND(3)
   return 0;
 }
