@@ -182,7 +182,8 @@ resources-own:
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
           tests/native/libhbtc_own_hosttest.so tests/native/libhbtc_msm_hosttest.so \
-          tests/native/libhbtc_rr_hosttest.so tests/native/libhbtc_rrw_hosttest.so
+          tests/native/libhbtc_rr_hosttest.so tests/native/libhbtc_rrw_hosttest.so \
+          tests/native/libhbtc_xadicw_hosttest.so
 # the 13 x 30 Fq code's host build (field.h FqR over fq_rr.h's plain 64-bit schedule, every MAD
 # checked for a carry-out) and the G1 decode with its square root on it
 tests/native/libhbtc_rr_hosttest.so: tests/native/hbtc_rr_hosttest.cpp tests/native/hbtc_rr_ops.h $(HDRS)
@@ -204,6 +205,17 @@ sanitize-rrw: | $(BUILD)
 	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
 	  tests/native/hbtc_rrw_host_main.cpp tests/native/hbtc_rrw_hosttest.cpp -o $(BUILD)/rrw_host_asan
 	$(BUILD)/rrw_host_asan $(RRW_TABLE)
+# the item pass's x-adic multiplication on the redundant form (curve.h xadic_mul_sac8_w: the packed
+# co-Z table chain, the column, the correction, the exit), both bounds tracked and asserted likewise
+tests/native/libhbtc_xadicw_hosttest.so: tests/native/hbtc_xadicw_hosttest.cpp tests/native/hbtc_xadicw_ops.h $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_xadicw_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+# (XADICW_TABLE=file runs the case table tests/xadicw_cases.py wrote and prints every result)
+.PHONY: sanitize-xadicw
+sanitize-xadicw: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_xadicw_host_main.cpp tests/native/hbtc_xadicw_hosttest.cpp -o $(BUILD)/xadicw_host_asan
+	$(BUILD)/xadicw_host_asan $(XADICW_TABLE)
 # msm_walk.h's host build (one wave of the lane-uniform bucket walk in lockstep, over a toy group
 # and over G1)
 tests/native/libhbtc_msm_hosttest.so: tests/native/hbtc_msm_hosttest.cpp $(HDRS)
@@ -269,7 +281,15 @@ $(BUILD)/hbtc_devtest.inl.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_devtest.call.o: tests/native/hbtc_devtest.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 devtest: tests/native/libhbtc_devtest.so tests/native/libhbtc_tree_devtest.so tests/native/libhbtc_rr_devtest.so \
-         tests/native/libhbtc_rrw_devtest.so
+         tests/native/libhbtc_rrw_devtest.so tests/native/libhbtc_xadicw_devtest.so
+# test-only device harness of the item pass's x-adic multiplication on the redundant form
+# (tests/test_gpu_xadicw.py): hbtc_xadicw_ops.h on 64-lane workgroups with k_rlc_items' LDS layout,
+# with the flags of hbtc_rlc.p6.o
+$(BUILD)/rr_devtest/hbtc_xadicw_devtest.o: tests/native/hbtc_xadicw_devtest.hip tests/native/hbtc_xadicw_ops.h $(HDRS) | $(BUILD)
+	mkdir -p $(BUILD)/rr_devtest
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE -c $< -o $@
+tests/native/libhbtc_xadicw_devtest.so: $(BUILD)/rr_devtest/hbtc_xadicw_devtest.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 # test-only device harness of the redundant 13 x 30 form (tests/test_gpu_rrw.py): the operations of
 # hbtc_rrw_ops.h on one workgroup, with the flags of hbtc_rlc.p6.o
 $(BUILD)/rr_devtest/hbtc_rrw_devtest.o: tests/native/hbtc_rrw_devtest.hip tests/native/hbtc_rrw_ops.h $(HDRS) | $(BUILD)

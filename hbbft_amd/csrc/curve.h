@@ -1379,6 +1379,260 @@ HDN bool g1_in_subgroup_t1_w(const G1A& p, G1J& t) {
   return jacw_eq_aff(t2, bx, ny);
 }
 
+// ------------------------------- the x-adic multiplication of the item pass on the redundant form
+// xadic_mul_sac8<Fq, true> for G1 (c = beta) with every Fq product on 13 x 30: the same recoding, the
+// same eight entries from the same co-Z sums in the same order, the same select tree over constant
+// indices, the same even-d0 correction and all-zero selection, so the exceptional-case argument above
+// xadic_table8 holds word for word.  Only the number form differs:
+//   - a table entry is a PACKED product result (fw_pack: below 1.5p on 12 words), 24 words like
+//     XY<Fq>, in registers and in LDS; the select tree runs on those words and only the selected
+//     entry is unpacked (shifts and masks) for the column's mixed addition;
+//   - every output of a co-Z sum is made a product result (the two coordinates of the sum by one
+//     product by R' each), so everything that is packed is one;
+//   - the accumulator is a JacW inside the invariant of jacw_dbl (every coordinate weakly
+//     normalised, <= 12p): a column is jacw_dbl, then jacw_madd_generic of an entry whose y may be
+//     negated (fw_neg: <= 4p);
+//   - p and xpj come in as 12 x 32 Montgomery values (5 products) and the result leaves as one (3).
+// tools/rr_bounds.py pushes the bounds through these schedules; the host build under
+// HBTC_RR_ASSERT asserts them at every operation.
+struct XYW {
+  FqW x, y;
+};
+// madd-2007-bl without the exceptional cases (jac_madd_generic's schedule): z3 = 2 Z1 H as a product
+HD void jacw_madd_generic(JacW& r, const JacW& p, const FqW& qx, const FqW& qy) {
+  FqW z1z1, u2, s2, H, HH, rr0, z3;
+  fw_sqr(z1z1, p.z);
+  fw_mul(u2, qx, z1z1);
+  fw_mul(s2, qy, p.z);
+  fw_mul(s2, s2, z1z1);
+  fw_sub(H, u2, p.x, rr::RR_SUB_2_14, 14);
+  fw_norm(H, H);
+  fw_sub(rr0, s2, p.y, rr::RR_SUB_2_14, 14);
+  fw_norm(rr0, rr0);
+  fw_sqr(HH, H);
+  fw_mul(z3, p.z, H);
+  fw_dbl(z3, z3);
+  fw_norm(z3, z3);
+  jacw_add_tail(r, p.x, p.y, H, HH, rr0, z3);
+}
+// coz_add on product results: s = A + B with A = (ax, ay) rescaled to the sum's Z; h is weakly
+// normalised (<= 5.5p), everything else that leaves is a product result
+HD void coz_add_w(XYW& s, FqW& ax, FqW& ay, FqW& h, const XYW& b) {
+  FqW r, hh, hhh, v, t, one;
+  fw_sub(h, b.x, ax, rr::RR_SUB_1_4, 4);
+  fw_norm(h, h);
+  fw_sub(r, b.y, ay, rr::RR_SUB_1_4, 4);
+  fw_norm(r, r);
+  fw_sqr(hh, h);
+  fw_mul(hhh, hh, h);
+  fw_mul(v, ax, hh);
+  fw_mul(ay, ay, hhh);
+  ax = v;
+  fw_sqr(t, r);
+  fw_sub(t, t, hhh, rr::RR_SUB_1_4, 4);
+  fw_norm(t, t);
+  fw_dbl(hh, v);
+  fw_sub(t, t, hh, rr::RR_SUB_2_4, 4);
+  fw_norm(t, t);  // the sum's x, <= 9.1p
+  fw_one(one);
+  fw_mul(s.x, t, one);
+  fw_sub(t, v, t, rr::RR_SUB_2_10, 10);
+  fw_norm(t, t);
+  fw_mul(t, r, t);
+  fw_sub(t, t, ay, rr::RR_SUB_1_4, 4);
+  fw_norm(t, t);
+  fw_mul(s.y, t, one);
+}
+HD void xyw_pack(XY<Fq>& r, const XYW& a) {
+  fw_pack(r.x, a.x);
+  fw_pack(r.y, a.y);
+}
+HD void xyw_unpack(XYW& r, const XY<Fq>& a) {
+  fw_unpack(r.x, a.x);
+  fw_unpack(r.y, a.y);
+}
+HD void xyw_rescale(XY<Fq>& p, const FqW& h2, const FqW& h3) {
+  FqW t;
+  fw_unpack(t, p.x);
+  fw_mul(t, t, h2);
+  fw_pack(p.x, t);
+  fw_unpack(t, p.y);
+  fw_mul(t, t, h3);
+  fw_pack(p.y, t);
+}
+HD void xyw_lds_rescale(uint32_t* lds, uint32_t lane, int e, const FqW& h2, const FqW& h3) {
+  XY<Fq> v;
+  xy_lds_get(v, lds, lane, e);
+  xyw_rescale(v, h2, h3);
+  xy_lds_put(lds, lane, e, v);
+}
+// xadic_table8_chain with packed entries: tab[0..4] in registers, entries 5..7 in LDS, zs packed
+HD void xadic_table8_chain_w(XY<Fq> tab[5], Fq& zsp, const G1A& p, const G1J& xpj, uint32_t* lds, uint32_t lane) {
+  XY<Fq>& P = tab[0];
+  XY<Fq>& S = tab[1];
+  XY<Fq> X;
+  FqW h, h2, h3, zs;
+  {  // P at XP's Z; S = XP + P (co-Z), XP updated; P rescaled: all three at Z0
+    FqW z, z2, z3;
+    XYW pw, xw, sw;
+    fw_from_fq(z, xpj.z);
+    fw_sqr(z2, z);
+    fw_mul(z3, z2, z);
+    fw_from_fq(pw.x, p.x);
+    fw_mul(pw.x, pw.x, z2);
+    fw_from_fq(pw.y, p.y);
+    fw_mul(pw.y, pw.y, z3);
+    fw_from_fq(xw.x, xpj.x);
+    fw_from_fq(xw.y, xpj.y);
+    coz_add_w(sw, xw.x, xw.y, h, pw);
+    xyw_pack(S, sw);
+    xyw_pack(X, xw);
+    fw_sqr(h2, h);
+    fw_mul(h3, h2, h);
+    fw_mul(pw.x, pw.x, h2);
+    fw_mul(pw.y, pw.y, h3);
+    xyw_pack(P, pw);
+    fw_mul(zs, z, h);
+  }
+  // out = U + m(V), U updated to the new Z; h2, h3 for the other entries
+  auto sum = [&](XY<Fq>& out, XY<Fq>& U, const XY<Fq>& V) {
+    XYW mv, u, o;
+    FqW beta;
+    fw_set(beta, rr::RR_BETA);
+    fw_unpack(mv.x, V.x);
+    fw_mul(mv.x, mv.x, beta);
+    fw_unpack(mv.y, V.y);
+    xyw_unpack(u, U);
+    coz_add_w(o, u.x, u.y, h, mv);
+    xyw_pack(out, o);
+    xyw_pack(U, u);
+    fw_sqr(h2, h);
+    fw_mul(h3, h2, h);
+    fw_mul(zs, zs, h);
+  };
+  // the order of xadic_table8_chain
+  sum(tab[4], P, X);  // P + m(XP)
+  xyw_rescale(X, h2, h3);
+  xyw_rescale(S, h2, h3);
+  {
+    XY<Fq> t5;
+    sum(t5, S, X);  // S + m(XP); XP is not needed past here
+    xy_lds_put(lds, lane, 0, t5);
+  }
+  xyw_rescale(P, h2, h3);
+  xyw_rescale(tab[4], h2, h3);
+  sum(tab[2], P, P);  // P + m(P)
+  xyw_rescale(S, h2, h3);
+  xyw_rescale(tab[4], h2, h3);
+  xyw_lds_rescale(lds, lane, 0, h2, h3);
+  sum(tab[3], S, P);  // S + m(P)
+  xyw_rescale(P, h2, h3);
+  xyw_rescale(tab[2], h2, h3);
+  xyw_rescale(tab[4], h2, h3);
+  xyw_lds_rescale(lds, lane, 0, h2, h3);
+  {
+    XY<Fq> t6;
+    sum(t6, P, S);  // P + m(S)
+    xy_lds_put(lds, lane, 1, t6);
+  }
+  xyw_rescale(S, h2, h3);
+  xyw_rescale(tab[2], h2, h3);
+  xyw_rescale(tab[3], h2, h3);
+  xyw_rescale(tab[4], h2, h3);
+  xyw_lds_rescale(lds, lane, 0, h2, h3);
+  {
+    XY<Fq> t7;
+    const XY<Fq> s0 = S;
+    sum(t7, S, s0);  // S + m(S)
+    xy_lds_put(lds, lane, 2, t7);
+  }
+  xyw_rescale(P, h2, h3);
+  xyw_rescale(tab[2], h2, h3);
+  xyw_rescale(tab[3], h2, h3);
+  xyw_rescale(tab[4], h2, h3);
+  xyw_lds_rescale(lds, lane, 0, h2, h3);
+  xyw_lds_rescale(lds, lane, 1, h2, h3);
+  fw_pack(zsp, zs);
+}
+// [d0 + d1 x + d2 mu + d3 mu x] p for p in G1 (not infinity) and xpj = [x] p, as xadic_mul_sac8<Fq,
+// true>: lds holds 3 x 24 x 64 words, [entry][word][lane].  r is a 12 x 32 Montgomery G1J, a
+// Jacobian representative of the same point as the 12 x 32 form's (another Z).
+HD void xadic_mul_sac8_w(G1J& r, const G1A& p, const G1J& xpj, uint32_t d0, uint32_t d1, uint32_t d2,
+                         uint32_t d3, int nbits, uint32_t* lds, uint32_t lane) {
+  constexpr int NWD = 24;
+  XY<Fq> tab[5];
+  Fq zsp;
+  xadic_table8_chain_w(tab, zsp, p, xpj, lds, lane);
+  const uint32_t k0 = d0 | 1u;
+  uint64_t m[3];
+  xadic_sac_recode(m, k0, d1, d2, d3, nbits);
+  // the entry of column i: the select tree on packed words, the selected entry unpacked, its y
+  // negated when s_i = -1
+  auto entry = [&](int i, XYW& t) {
+    const bool b1 = ((m[0] >> i) & 1u) != 0, b2 = ((m[1] >> i) & 1u) != 0;
+    const bool b3 = ((m[2] >> i) & 1u) != 0;
+    XY<Fq> e0, e1, e;
+    {
+      XY<Fq> a, b;
+      xy_sel(a, b1, tab[1], tab[0]);
+      xy_sel(b, b1, tab[3], tab[2]);
+      xy_sel(e0, b2, b, a);
+    }
+    {
+      const uint32_t j = (b1 ? 1u : 0u) + (b2 ? 2u : 0u);  // entry 4 + j
+      const uint32_t li = j ? j - 1u : 0u;
+      XY<Fq> l;
+      uint32_t* dst = reinterpret_cast<uint32_t*>(&l);
+#pragma unroll
+      for (int w = 0; w < NWD; ++w) dst[w] = lds[(li * NWD + w) * 64 + lane];
+      xy_sel(e1, j != 0, l, tab[4]);
+    }
+    xy_sel(e, b3, e1, e0);
+    xyw_unpack(t, e);
+    const bool neg = i < nbits && (((uint64_t)k0 >> (i + 1)) & 1u) == 0;
+    FqW ny;
+    fw_neg(ny, t.y);
+    fw_sel(t.y, neg, ny, t.y);
+  };
+  JacW acc;
+  {
+    XYW t;
+    entry(nbits, t);  // s = +1
+    acc.x = t.x;
+    acc.y = t.y;
+    fw_one(acc.z);
+  }
+#pragma unroll 1
+  for (int i = nbits - 1; i >= 0; --i) {
+    jacw_dbl(acc, acc);
+    XYW t;
+    entry(i, t);
+    jacw_madd_generic(acc, acc, t.x, t.y);
+  }
+  {  // d0 even: acc - P (P = tab[0] on the isomorphic curve)
+    const bool even = (d0 & 1u) == 0;
+    const bool zero = (d0 | d1 | d2 | d3) == 0;
+    XYW t;
+    xyw_unpack(t, tab[0]);
+    FqW ny;
+    fw_neg(ny, t.y);
+    JacW n;
+    jacw_madd_generic(n, acc, t.x, ny);
+    fw_sel(acc.x, even, n.x, acc.x);
+    fw_sel(acc.y, even, n.y, acc.y);
+    fw_sel(acc.z, even, n.z, acc.z);
+    FqW z0;
+    fw_zero(z0);
+    fw_sel(acc.z, zero, z0, acc.z);
+  }
+  {
+    FqW zs;
+    fw_unpack(zs, zsp);
+    fw_mul(acc.z, acc.z, zs);  // back from the isomorphic curve
+  }
+  jacw_to_jac(r, acc);
+}
+
 HD void g2_psi(Fq2& rx, Fq2& ry, const G2A& p) {
   Fq2 c, k;
   fq2_conj(c, p.x);

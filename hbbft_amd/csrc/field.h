@@ -73,9 +73,10 @@
 // The product and squaring on 13 limbs of 30 bits (tools/gen_fq_rr.py): no carry word per MAC.
 // HBTC_FQ_RR=1 runs the square root of k_rlc_decode's G1 decode on it (FqR below); 2 also runs the
 // two |x| chains of that kernel's subgroup test on its redundant form (FqW below, curve.h jacw_*);
-// 0 builds the 12 x 32 code everywhere, for comparisons.
+// 3 also runs k_rlc_items' x-adic multiplication there (curve.h xadic_mul_sac8_w); 0 builds the
+// 12 x 32 code everywhere, for comparisons.
 #ifndef HBTC_FQ_RR
-#define HBTC_FQ_RR 2
+#define HBTC_FQ_RR 3
 #endif
 #include "fq_rr.h"
 
@@ -992,6 +993,42 @@ HD void fw_to_fq(Fq& r, const FqW& a) {  // a R' (weakly normalised, <= 64p) -> 
 #pragma unroll
   for (int i = 0; i < 13; ++i) u.v[i] = t.v[i];
   fqr_limbs32(r, u);
+}
+HD void fw_sel(FqW& r, bool c, const FqW& a, const FqW& b) {  // r = c ? a : b, the bounds the larger
+#if HBTC_FW_TRACK
+  uint64_t lb[13];
+  for (int i = 0; i < 13; ++i) lb[i] = a.lb[i] > b.lb[i] ? a.lb[i] : b.lb[i];
+  const uint64_t vb = a.vb > b.vb ? a.vb : b.vb;
+#endif
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = c ? a.v[i] : b.v[i];
+#if HBTC_FW_TRACK
+  fw_set_bounds(r, lb, vb);
+#endif
+}
+// A product result below 1.5p (limbs < 2^30, so the integer is below 2^384) on 12 words: the same
+// integer re-limbed by shifts, no product.  The x-adic table of the item pass keeps its entries so
+// (curve.h xadic_mul_sac8_w): 24 words an entry like XY<Fq>, in the R' domain.  Not a 12 x 32
+// Montgomery value: only fw_unpack reads it.
+HD void fw_pack(Fq& r, const FqW& a) {
+#if HBTC_FW_TRACK
+  for (int i = 0; i < 13; ++i)
+    if (a.lb[i] > rr::RR_MASK) fw_fail("packing limbs above 2^30 - 1");
+  if (a.vb > FW_ONE_P + FW_ONE_P / 2) fw_fail("packing a value that may pass 1.5p");
+#endif
+  FqR t;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) t.v[i] = a.v[i];
+  fqr_limbs32(r, t);
+}
+HD void fw_unpack(FqW& r, const Fq& a) {
+  FqR t;
+  fqr_limbs30(t, a);
+#pragma unroll
+  for (int i = 0; i < 13; ++i) r.v[i] = t.v[i];
+#if HBTC_FW_TRACK
+  fw_set_strict(r, FW_ONE_P + FW_ONE_P / 2);
+#endif
 }
 
 // canonical(a) > (p-1)/2  <=>  a > -a  (pairing 0.14 ordering on canonical values, a != 0)

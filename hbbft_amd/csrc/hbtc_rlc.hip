@@ -284,7 +284,14 @@ __global__ void __launch_bounds__(64, HBTC_ITEMS_WAVES) k_rlc_items(
       Fq beta;
       fq_set(beta, G1_BETA);
 #if HBTC_XADIC8
-#if HBTC_ITEMS_WAVES >= 2 && HBTC_SAC8_LDS
+#if HBTC_ITEMS_WAVES >= 2 && HBTC_SAC8_LDS && HBTC_FQ_RR >= 3 && HBTC_RLC_SPLIT && HBTC_RLC_TREE
+      // the same multiplication with its Fq products on the redundant 13 x 30 form and the table
+      // packed on the same 24 words an entry (curve.h xadic_mul_sac8_w): S is another Jacobian
+      // representative of the same point, on the same 12 x 32 Montgomery words
+      (void)beta;
+      xadic_mul_sac8_w(S, d, t1, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits,
+                       reinterpret_cast<uint32_t*>(red), lane);
+#elif HBTC_ITEMS_WAVES >= 2 && HBTC_SAC8_LDS
       xadic_mul_sac8<Fq, true>(S, d, t1, beta, xd.d[0], xd.d[1], xd.d[2], xd.d[3], xd.nbits,
                                reinterpret_cast<uint32_t*>(red), lane);
 #else

@@ -64,6 +64,10 @@ W_SLACK = 3
 W_VMAX = 64
 W_LIMBS = [M + W_SLACK] * (N - 1) + [(W_VMAX * P_MOD) >> (W * (N - 1))]
 ONE = (1 << RBITS) % P_MOD                                     # the Montgomery one, R' mod p
+# beta of the G1 endomorphism phi(x, y) = (beta x, y) (tools/gen_constants.py G1_BETA), for the table
+# of the x-adic multiplication on this form (curve.h xadic_mul_sac8_w)
+BETA = 0x5f19672fdf76ce51ba69c6076a0f77eaddb3a93be6f89688de17d813620a00022e01fffffffefffe
+assert pow(BETA, 3, P_MOD) == 1 and BETA != 1
 
 
 def sub_const(b, k):
@@ -381,6 +385,7 @@ HBTC_RR_CONST uint32_t RR_W_SLACK = %du;
 HBTC_RR_CONST uint32_t RR_W_TOP = 0x%08xu;""" % (W_SLACK, W_LIMBS[N - 1], W_VMAX, wm["splits"], wsq["splits"],
                                                    W_SLACK, W_LIMBS[N - 1]))
     print(arr("RR_ONE", limbs(ONE)) + "  // 2^390 mod p: the Montgomery one")
+    print(arr("RR_BETA", limbs(BETA * ONE % P_MOD)) + "  // beta 2^390 mod p (bls_constants.h G1_BETA on this form)")
     for b, k in SUB_CONSTS:
         print(arr("RR_SUB_%d_%d" % (b, k), sub_const(b, k)) +
               "  // %d p with %d borrowed per limb: a + this - s for limbs of s <= these" % (k, b))

@@ -5,7 +5,9 @@
 // one-block 12 x 32 forms at 1 / 2 / 3 waves per SIMD, and one jac_dbl step on 12 x 32 (curve.h jac_dbl)
 // against the redundant 13 x 30 form (jacw_dbl) at the same occupancies (for this A/B build with
 // -DHBTC_INLINE_ALL -DHBTC_FQMUL_INLINE, the flags of k_rlc_decode's object: the 12 x 32 doubling then
-// has its products inlined as in that kernel).  Prints time, Fqm/s and the fraction of the measured
+// has its products inlined as in that kernel), and one column of k_rlc_items' double-and-add (doubling,
+// select tree over five register and three LDS entries, mixed addition) on 12 x 32 against the packed
+// table + redundant form of xadic_mul_sac8_w, on 64-lane workgroups as in that kernel.  Prints time, Fqm/s and the fraction of the measured
 // v_mad_u64_u32 roofline (29.51e12 / 288 Fqm/s), plus a cross-check of the three results.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -124,6 +126,112 @@ __global__ void __launch_bounds__(256, WAVES) k_dblw(const FqR* in, FqR* out, in
     out[3 * (size_t)i].v[l] = p.x.v[l];
     out[3 * (size_t)i + 1].v[l] = p.y.v[l];
     out[3 * (size_t)i + 2].v[l] = p.z.v[l];
+  }
+}
+
+// One COLUMN of k_rlc_items' double-and-add per iteration: a doubling, the select tree over the 8-entry
+// table (five entries in registers, three in LDS laid out [entry][word][lane], 64-lane workgroups as in
+// the kernel), the sign, the branch-free mixed addition.  RRW false: jac_dbl + jac_madd_generic on 12 x 32
+// (curve.h xadic_mul_sac8<Fq, true>'s column); true: the packed table, the selected entry unpacked,
+// jacw_dbl + jacw_madd_generic (xadic_mul_sac8_w's column).  The entries are arbitrary field elements
+// below 2^380 (the cost does not depend on their being curve points); bit k of `bits` is the column's
+// u_(k+1), bit 3 its sign.
+constexpr int COL_ITERS = 32;
+HD uint32_t col_bits(uint32_t i, int it) { return (i * 2654435761u + (uint32_t)it * 0x9e3779b9u) >> 27; }
+HD void col_entry(XY<Fq>& t, const XY<Fq> tab[5], const uint32_t* lds, uint32_t lane, uint32_t bits) {
+  const bool b1 = bits & 1u, b2 = bits & 2u, b3 = bits & 4u;
+  XY<Fq> e0, e1;
+  {
+    XY<Fq> a, b;
+    xy_sel(a, b1, tab[1], tab[0]);
+    xy_sel(b, b1, tab[3], tab[2]);
+    xy_sel(e0, b2, b, a);
+  }
+  {
+    const uint32_t j = (b1 ? 1u : 0u) + (b2 ? 2u : 0u);
+    const uint32_t li = j ? j - 1u : 0u;
+    XY<Fq> l;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&l);
+#pragma unroll
+    for (int w = 0; w < 24; ++w) dst[w] = lds[(li * 24 + w) * 64 + lane];
+    xy_sel(e1, j != 0, l, tab[4]);
+  }
+  xy_sel(t, b3, e1, e0);
+}
+HD void col12(G1J& acc, const XY<Fq> tab[5], const uint32_t* lds, uint32_t lane, uint32_t bits) {
+  jac_dbl(acc, acc);
+  XY<Fq> t;
+  col_entry(t, tab, lds, lane, bits);
+  Fq ny;
+  fneg(ny, t.y);
+  fsel(t.y, (bits & 8u) != 0, ny, t.y);
+  jac_madd_generic(acc, acc, t.x, t.y);
+}
+HD void colw(JacW& acc, const XY<Fq> tab[5], const uint32_t* lds, uint32_t lane, uint32_t bits) {
+  jacw_dbl(acc, acc);
+  XY<Fq> t;
+  col_entry(t, tab, lds, lane, bits);
+  XYW w;
+  xyw_unpack(w, t);
+  FqW ny;
+  fw_neg(ny, w.y);
+  fw_sel(w.y, (bits & 8u) != 0, ny, w.y);
+  jacw_madd_generic(acc, acc, w.x, w.y);
+}
+// the table of item i from the 1024 inputs: entries 0..4 to tab, 5..7 to the lane's LDS column
+HD void col_table(XY<Fq> tab[5], uint32_t* lds, uint32_t lane, uint32_t i, const Fq* in) {
+  for (int e = 0; e < 8; ++e) {
+    XY<Fq> v;
+    v.x = in[(i + 2 * e) & 1023];
+    v.y = in[(i + 2 * e + 1) & 1023];
+    if (e < 5) tab[e] = v;
+    else xy_lds_put(lds, lane, e - 5, v);
+  }
+}
+HD void col_run12(uint32_t* o, uint32_t i, uint32_t lane, uint32_t* lds, const Fq* in, int n) {
+  XY<Fq> tab[5];
+  col_table(tab, lds, lane, i, in);
+  G1J p;
+  p.x = in[(i + 16) & 1023];
+  p.y = in[(i + 17) & 1023];
+  p.z = in[(i + 18) & 1023];
+#pragma unroll 1
+  for (int it = 0; it < n; ++it) col12(p, tab, lds, lane, col_bits(i, it));
+  Fq c[3];
+  fq_canon(c[0], p.x);
+  fq_canon(c[1], p.y);
+  fq_canon(c[2], p.z);
+  for (int j = 0; j < 3; ++j)
+    for (int l = 0; l < 12; ++l) o[12 * j + l] = c[j].v[l];
+}
+HD void col_runw(uint32_t* o, uint32_t i, uint32_t lane, uint32_t* lds, const Fq* in, const FqR* in13, int n) {
+  XY<Fq> tab[5];
+  col_table(tab, lds, lane, i, in);
+  JacW p;
+  for (int l = 0; l < 13; ++l) {
+    p.x.v[l] = in13[i & 1023].v[l];
+    p.y.v[l] = in13[(i + 1) & 1023].v[l];
+    p.z.v[l] = in13[(i + 2) & 1023].v[l];
+  }
+#pragma unroll 1
+  for (int it = 0; it < n; ++it) colw(p, tab, lds, lane, col_bits(i, it));
+  for (int l = 0; l < 13; ++l) {
+    o[l] = p.x.v[l];
+    o[13 + l] = p.y.v[l];
+    o[26 + l] = p.z.v[l];
+  }
+}
+template <int WAVES, bool RRW>
+__global__ void __launch_bounds__(64, WAVES) k_col(const Fq* in, const FqR* in13, uint32_t* out, int n) {
+  __shared__ uint32_t lds[3 * 24 * 64];
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * 64 + lane;
+  uint32_t o[39];
+  if constexpr (RRW) {
+    col_runw(o, i, lane, lds, in, in13, n);
+    for (int k = 0; k < 39; ++k) out[39 * (size_t)i + k] = o[k];
+  } else {
+    col_run12(o, i, lane, lds, in, n);
+    for (int k = 0; k < 36; ++k) out[36 * (size_t)i + k] = o[k];
   }
 }
 
@@ -322,5 +430,50 @@ int main() {
   RUND(1)
   RUND(2)
   RUND(3)
+  // one column of k_rlc_items (64-lane workgroups, 18,432 B of LDS each): 4 columns of 64 lanes
+  // cross-checked against the host build of the same functions, then 12 x 32 against the redundant form in
+  // the same run; blocks = 256 CUs x 4 SIMDs x W
+  {
+    const int K = 4;
+    std::vector<uint32_t> g12(36 * 64), gw(39 * 64), lds(3 * 24 * 64);
+    uint32_t* o12 = reinterpret_cast<uint32_t*>(d_out);
+    uint32_t* ow = reinterpret_cast<uint32_t*>(d_out13);
+    hipLaunchKernelGGL((k_col<1, false>), dim3(1), dim3(64), 0, 0, d_in, d_in13, o12, K);
+    CHK(hipMemcpy(g12.data(), o12, 4 * 36 * 64, hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL((k_col<1, true>), dim3(1), dim3(64), 0, 0, d_in, d_in13, ow, K);
+    CHK(hipMemcpy(gw.data(), ow, 4 * 39 * 64, hipMemcpyDeviceToHost));
+    int bad12 = 0, badw = 0;
+    for (uint32_t i = 0; i < 64; ++i) {
+      uint32_t o[39];
+      col_run12(o, i, i, lds.data(), h.data(), K);
+      for (int k = 0; k < 36; ++k) bad12 += o[k] != g12[36 * i + k];
+      col_runw(o, i, i, lds.data(), h.data(), hr13.data(), K);
+      for (int k = 0; k < 39; ++k) badw += o[k] != gw[39 * i + k];
+    }
+    printf("cross-check column vs host: 12x32 %s (%d limb mismatches), redundant 13x30 %s (%d)\n",
+           bad12 ? "FAIL" : "ok", bad12, badw ? "FAIL" : "ok", badw);
+    auto runc = [&](const char* name, auto launch, int blocks) {
+      launch(blocks);
+      CHK(hipDeviceSynchronize());
+      CHK(hipEventRecord(a));
+      launch(blocks);
+      CHK(hipEventRecord(b));
+      CHK(hipEventSynchronize(b));
+      float ms;
+      CHK(hipEventElapsedTime(&ms, a, b));
+      printf("%-40s blocks=%5d %8.3f ms %9.3e columns/s\n", name, blocks, ms,
+             (double)blocks * 64 * COL_ITERS / (ms * 1e-3));
+    };
+#define RUNC(W)                                                                                                   \
+  runc("A/B column 12x32 " #W "w/SIMD",                                                                           \
+       [&](int bl) { hipLaunchKernelGGL((k_col<W, false>), dim3(bl), dim3(64), 0, 0, d_in, d_in13, o12, COL_ITERS); }, \
+       1024 * W);                                                                                                 \
+  runc("A/B column 13x30 redundant " #W "w/SIMD",                                                                 \
+       [&](int bl) { hipLaunchKernelGGL((k_col<W, true>), dim3(bl), dim3(64), 0, 0, d_in, d_in13, ow, COL_ITERS); },  \
+       1024 * W);
+    RUNC(1)
+    RUNC(2)
+    RUNC(3)
+  }
   return 0;
 }

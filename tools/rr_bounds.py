@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Bounds interpreter of the point formulas on the redundant 13 x 30 form (field.h FqW, curve.h
-jacw_dbl / jacw_add_aff / jacw_add / jacw_eq_aff).
+jacw_dbl / jacw_add_aff / jacw_add / jacw_eq_aff, and xadic_mul_sac8_w with its table chain).
 
 The formulas are written once, over an abstract set of field operations, in the order and with the
 normalisations and subtraction constants of curve.h.  Two implementations of the operations run them:
@@ -13,6 +13,8 @@ normalisations and subtraction constants of curve.h.  Two implementations of the
 
 check_closure() shows that from the declared loop-entry bound ENTRY every output of jacw_dbl and of
 both additions, with and without the special-case exits, is inside ENTRY again.
+check_items_closure() does the same for the item pass's x-adic multiplication (curve.h
+xadic_mul_sac8_w): the packed table chain, the column, the even-d0 correction and the exit.
 
 Usage: tools/rr_bounds.py            (prints the bound of every output and "closure ok")
 """
@@ -26,6 +28,7 @@ import gen_fq_rr as G  # noqa: E402
 N, W, M, P = G.N, G.W, G.M, G.P_MOD
 U32 = (1 << 32) - 1
 X_ABS = 0xd201000000010000      # |x| of BLS12-381
+PACK_V = Fraction(3, 2)          # everything that is packed (field.h fw_pack) is a product result below 1.5p
 ENTRY_V = 12                     # the loop invariant: every coordinate of the accumulator <= 12 p,
 BASE_V = 12                      # of a Jacobian base likewise; an affine base is a product result
 
@@ -123,6 +126,23 @@ class Bounds:
             raise BoundsError("comparison of %r and %r" % (a, b))
         return True
 
+    def sel(self, c, a, b):
+        """either of the two: the larger bound, limb by limb"""
+        return Bd([max(x, y) for x, y in zip(a.l, b.l)], max(a.v, b.v))
+
+    def const(self, v):
+        """a constant below p on limbs < 2^30 (fq_rr.h RR_BETA, RR_K_OUT)"""
+        return strict(1)
+
+    def pack(self, a):
+        """field.h fw_pack: only a product result below 1.5p goes onto 12 words"""
+        if max(a.l) > M or a.v > PACK_V:
+            raise BoundsError("packing %r" % (a,))
+        return a
+
+    def unpack(self, a):
+        return strict(PACK_V)
+
 
 def val(l):
     return sum(x << (W * i) for i, x in enumerate(l))
@@ -167,6 +187,20 @@ class Limbs:
     def canon_eq(self, a, b):
         assert val(a) < 2 * P and val(b) < 2 * P
         return val(a) % P == val(b) % P
+
+    def sel(self, c, a, b):
+        return a if c else b
+
+    def const(self, v):
+        return G.limbs(v * G.ONE % P)
+
+    def pack(self, a):
+        """12 words of 32 bits and back: the same limbs when the integer is below 2^384"""
+        assert max(a) <= M and val(a) < 1 << 384
+        return G.limbs(val(a) & ((1 << 384) - 1))
+
+    def unpack(self, a):
+        return a
 
 
 # ------------------------------------------------------------------------------ the formulas
@@ -276,6 +310,136 @@ def jacw_mul_x(o, q, affine, k=X_ABS):
     return acc
 
 
+# --------------------------------------- the x-adic multiplication of the item pass (xadic_mul_sac8_w)
+def neg(o, a):
+    """fw_neg: a product result or constant (strict limbs, below 3p) -> weakly normalised, <= 4p"""
+    return o.norm(o.sub(o.zero(), a, S1))
+
+
+def jacw_madd_generic(o, p, qx, qy):
+    """madd-2007-bl without the exceptional cases (jac_madd_generic's schedule): Z3 = 2 Z1 H as a product"""
+    X, Y, Z = p
+    z1z1 = o.sqr(Z)
+    u2 = o.mul(qx, z1z1)
+    s2 = o.mul(o.mul(qy, Z), z1z1)
+    H = o.norm(o.sub(u2, X, S2D))
+    rr = o.norm(o.sub(s2, Y, S2D))
+    HH = o.sqr(H)
+    z3 = o.norm(o.dbl(o.mul(Z, H)))
+    return _add_tail(o, p, X, Y, H, HH, rr, z3)
+
+
+def coz_add_w(o, a, b):
+    """co-Z sum of product results a and b: (the sum, a at the sum's Z, h); all product results but h"""
+    ax, ay = a
+    h = o.norm(o.sub(b[0], ax, S1))
+    r = o.norm(o.sub(b[1], ay, S1))
+    hh = o.sqr(h)
+    hhh = o.mul(hh, h)
+    v = o.mul(ax, hh)
+    ay = o.mul(ay, hhh)
+    t = o.norm(o.sub(o.sqr(r), hhh, S1))
+    t = o.norm(o.sub(t, o.dbl(v), S2))
+    one = o.one()
+    sx = o.mul(t, one)
+    t = o.norm(o.sub(v, t, S2C))
+    t = o.norm(o.sub(o.mul(r, t), ay, S1))
+    return (sx, o.mul(t, one)), (v, ay), h
+
+
+def xadic_table8_chain_w(o, p, xpj):
+    """The eight packed entries (slot u1 + 2 u2 + 4 u3) and the packed Z* from p = (x, y) and xpj = (X, Y, Z)
+    as fw_from_fq leaves them, in the order of curve.h xadic_table8_chain_w."""
+    beta = o.const(G.BETA)
+    pk = lambda e: (o.pack(e[0]), o.pack(e[1]))
+    up = lambda e: (o.unpack(e[0]), o.unpack(e[1]))
+    z = xpj[2]
+    z2 = o.sqr(z)
+    z3 = o.mul(z2, z)
+    pw = (o.mul(p[0], z2), o.mul(p[1], z3))
+    sw, xw, h = coz_add_w(o, (xpj[0], xpj[1]), pw)
+    T = {"S": pk(sw), "X": pk(xw)}
+    st = {"h2": o.sqr(h)}
+    st["h3"] = o.mul(st["h2"], h)
+    T["P"] = pk((o.mul(pw[0], st["h2"]), o.mul(pw[1], st["h3"])))
+    st["zs"] = o.mul(z, h)
+
+    def rescale(*names):
+        for n in names:
+            e = up(T[n])
+            T[n] = pk((o.mul(e[0], st["h2"]), o.mul(e[1], st["h3"])))
+
+    def sum_(out, U, V):
+        v = up(T[V])
+        mv = (o.mul(v[0], beta), v[1])
+        s, u, h = coz_add_w(o, up(T[U]), mv)
+        T[out], T[U] = pk(s), pk(u)
+        st["h2"] = o.sqr(h)
+        st["h3"] = o.mul(st["h2"], h)
+        st["zs"] = o.mul(st["zs"], h)
+
+    sum_(4, "P", "X")
+    rescale("X", "S")
+    sum_(5, "S", "X")
+    rescale("P", 4)
+    sum_(2, "P", "P")
+    rescale("S", 4, 5)
+    sum_(3, "S", "P")
+    rescale("P", 2, 4, 5)
+    sum_(6, "P", "S")
+    rescale("S", 2, 3, 4, 5)
+    sum_(7, "S", "S")
+    rescale("P", 2, 3, 4, 5, 6)
+    tab = [T["P"], T["S"]] + [T[k] for k in range(2, 8)]
+    return tab, o.pack(st["zs"])
+
+
+def sac_recode(k0, d, nbits):
+    """curve.h xadic_sac_recode: bit i of m[j] = u_(j+1)[i]"""
+    m = []
+    for k in d:
+        mk = 0
+        for i in range(nbits + 1):
+            odd = k & 1
+            negi = ((~k0 >> (i + 1)) & 1) if i < nbits else 0
+            mk |= odd << i
+            k = (k >> 1) + (odd & negi)
+        m.append(mk)
+    return m
+
+
+def column(o, acc, e, negate):
+    """one column: a doubling, then the mixed addition of the unpacked entry, its y negated or not"""
+    acc = jacw_dbl(o, acc)
+    x, y = o.unpack(e[0]), o.unpack(e[1])
+    y = o.sel(negate, neg(o, y), y)
+    return jacw_madd_generic(o, acc, x, y)
+
+
+def xadic_mul_sac8_w(o, p, xpj, d, nbits):
+    """[d0 + d1 x + d2 mu + d3 mu x] p as curve.h xadic_mul_sac8_w runs it; the three coordinates as
+    fw_to_fq's product by R leaves them, still on 13 limbs"""
+    tab, zsp = xadic_table8_chain_w(o, p, xpj)
+    k0 = d[0] | 1
+    m = sac_recode(k0, d[1:], nbits)
+    ent = lambda i: tab[((m[0] >> i) & 1) + 2 * ((m[1] >> i) & 1) + 4 * ((m[2] >> i) & 1)]
+    e = ent(nbits)
+    acc = (o.unpack(e[0]), o.unpack(e[1]), o.one())
+    for i in range(nbits - 1, -1, -1):
+        acc = column(o, acc, ent(i), ((k0 >> (i + 1)) & 1) == 0)
+    return correction_and_exit(o, acc, tab[0], zsp, d)
+
+
+def correction_and_exit(o, acc, p0, zsp, d):
+    even, zero = d[0] & 1 == 0, not any(d)
+    n = jacw_madd_generic(o, acc, o.unpack(p0[0]), neg(o, o.unpack(p0[1])))
+    acc = tuple(o.sel(even, a, b) for a, b in zip(n, acc))
+    z = o.sel(zero, o.zero(), acc[2])
+    z = o.mul(z, o.unpack(zsp))
+    kout = o.const(G.K_OUT * pow(G.ONE, -1, P) % P)
+    return tuple(o.mul(c, kout) for c in (acc[0], acc[1], z))
+
+
 # --------------------------------------------------------------------------------- closure
 def paths():
     yield {}
@@ -307,6 +471,35 @@ def check_closure(formulas=None, verbose=False):
     return True
 
 
+def check_items_closure(verbose=False):
+    """xadic_mul_sac8_w: the table chain from fw_from_fq's outputs (every packed value a product result
+    below 1.5p: Bounds.pack refuses anything else), then from the entry bound one column -- a doubling and
+    the mixed addition of an entry whose y is negated or not -- back inside the entry bound, the first
+    column from the entry itself, the even-d0 correction and the exit."""
+    o = Bounds()
+    fq = strict(PACK_V)                                        # fw_from_fq: a product result < 1.5 p
+    tab, zsp = xadic_table8_chain_w(o, (fq, fq), (fq, fq, fq))
+    assert len(tab) == 8
+    ent = entry()
+    e = (strict(PACK_V), strict(PACK_V))
+    for start in ((ent, ent, ent), (o.unpack(e[0]), o.unpack(e[1]), o.one())):
+        out = column(o, start, e, True)
+        for c, b in zip("XYZ", out):
+            if verbose:
+                print("column   %s: %r" % (c, b))
+            if not b.within(ent):
+                raise BoundsError("column %s leaves the entry bound: %r" % (c, b))
+    out = correction_and_exit(o, (ent, ent, ent), e, zsp, (0, 0, 0, 0))
+    for c, b in zip("XYZ", out):
+        if verbose:
+            print("exit     %s: %r" % (c, b))
+        if max(b.l) > M or b.v >= 2:
+            raise BoundsError("exit %s is not a product result below 2p: %r" % (c, b))
+    return True
+
+
 if __name__ == "__main__":
     check_closure(verbose=True)
     print("closure ok: entry %r" % entry())
+    check_items_closure(verbose=True)
+    print("item pass: table chain, column, correction and exit ok")
