@@ -20,7 +20,8 @@ SKG_PARTS := 10
 KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_PARTS),$(BUILD)/hbtc_rlc.p$(p).o) \
          $(foreach p,$(MSM_PARTS),$(BUILD)/hbtc_msm.p$(p).o) $(foreach p,$(SKG_PARTS),$(BUILD)/hbtc_skg.p$(p).o) \
          $(BUILD)/hbtc_check.c1.o $(BUILD)/hbtc_check.c2.o $(BUILD)/hbtc_sig.s1.o $(BUILD)/hbtc_sig.s2.o $(BUILD)/hbtc_pb.o \
-         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o $(BUILD)/hbtc_own.o
+         $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o $(BUILD)/hbtc_own.o \
+         $(BUILD)/hbtc_sv.o
 LIB := hbbft_amd/libhbtc.so
 
 .PHONY: all lib hosttest devtest oracle clean resources roofline-constants
@@ -126,6 +127,12 @@ $(BUILD)/hbtc_keygen.o: $(CSRC)/hbtc_keygen.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_own.o: $(CSRC)/hbtc_own.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
 
+# signed messages grouped by signer (k_sv_items: cofactor clearing and two x-adic G2 multiplications
+# per item on lane pairs; the signers' trees): the flag set of hbtc_enc.o (`make resources-sv` prints
+# the resource report)
+$(BUILD)/hbtc_sv.o: $(CSRC)/hbtc_sv.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
+
 # Reliable Broadcast: Reed-Solomon over GF(2^8), SHA3 Merkle trees and proofs
 $(BUILD)/hbtc_bcast.o: $(CSRC)/hbtc_bcast.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -178,6 +185,11 @@ resources-keygen:
 resources-own:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_own.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
+
+.PHONY: resources-sv
+resources-sv:
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_sv.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"
 
 hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so tests/native/libhbtc_dec_hosttest.so \
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \

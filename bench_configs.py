@@ -57,6 +57,15 @@ checked against the construction after timing:
       hash_g2_batch + g2_mul.  Reports median / minimum per path, the HIP-event spans of
       "own_dec" / "own_sig" and their stages, and the ratio to the CPU baseline's 2,593 pair
       checks/s as context.
+  sv  DynamicHoneyBadger's signed votes and key-gen messages (not in the default list): 65,536 items
+      spread evenly over 1,000 signers, interleaved, one of them rejected, at message sizes of 128 B
+      (votes) and 4 KB.  hbtc_verify_signed_msgs -- its grouped path (hbtc_set_exact_below(0): sums
+      per signer) and the route it takes by default -- against the composed calls on the same inputs,
+      hbtc_hash_g2_batch_gpu + hbtc_verify_sigs, in the same process, interleaved in every repeat
+      after a warm-up, statuses compared.  Host buffers and
+      the Python marshalling are inside the timed region.  Reports median / minimum per path, the
+      ratio and the HIP-event spans ("sv_items", "sv_sums", "sv_checks", "hash" and the exact
+      route's families).
 
   bc  Reliable Broadcast of one HoneyBadger epoch at N = 256 (the largest network hbbft's
       reed-solomon-erasure coding accepts: k + p <= 256), one node's view: the N^2 = 65,536 Echo
@@ -67,7 +76,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own,sv] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -1104,6 +1113,107 @@ def bench_own_shares(ctx, v_bytes, steps, warmup):
     return res
 
 
+def bench_signed_msgs(ctx, steps, warmup, n_signers=1000, n_items=1 << 16):
+    """sv: hbtc_verify_signed_msgs against the composed calls it replaces (see the docstring)."""
+    rng = random.Random(SEED + 17)
+    nrng = np.random.default_rng(SEED + 17)
+    sks = [rng.randrange(1, R) for _ in range(n_signers)]
+    pk, st = ctx.g1_mul(G1_GEN, fr_bytes(sks))
+    assert not st.any()
+    pkb = pk.tobytes()
+    pks = [pkb[48 * j:48 * j + 48] for j in range(n_signers)]
+    ks, bad = ctx.keyset_load(pks)
+    assert bad == 0
+    steps = max(steps, 5)
+    families = ("sv_items", "sv_sums", "sv_checks", "hash", "pb_items", "pb_lines", "pb_ml", "pb_checks",
+                "pb_decode", "sig_items", "chk_leaves", "rlc_finalize")
+
+    def stat(xs):
+        return {"median_ms": round(float(np.median(xs)), 3), "min_ms": round(min(xs), 3),
+                "max_ms": round(max(xs), 3)}
+
+    def spans(fn):
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        fn()
+        out = {}
+        for fam in families:
+            ms, launches = ctx.timing_read(fam)
+            if launches:
+                out[fam] = {"ms": round(ms, 3), "launches": int(launches)}
+        ctx.timing_enable(False)
+        return out
+
+    out = {}
+    signer = [i % n_signers for i in range(n_items)]  # spread evenly, interleaved
+    for size in (128, 4096):
+        t0 = time.time()
+        msgs = [nrng.integers(0, 256, size, dtype=np.uint8).tobytes() for _ in range(n_items)]
+        sigs = [None] * n_items
+        for j in range(n_signers):
+            mine = list(range(j, n_items, n_signers))
+            for i, sg in zip(mine, ctx.sign_shares(sks[j], [msgs[i] for i in mine], want_H=False)[0]):
+                sigs[i] = sg
+        sigs[n_items // 2] = sigs[n_items // 2 + n_signers]  # one signature of another message
+        item_pks = [pks[j] for j in signer]
+        log("sv: setup %.1fs (%d items of %d bytes, %d signers)" % (time.time() - t0, n_items, size, n_signers))
+        last = {}
+
+        def grouped():  # hbtc_set_exact_below(0) selects the grouped path
+            ctx.set_exact_below(0)
+            try:
+                last["new"] = ctx.verify_signed_msgs(ks, signer, msgs, sigs)
+            finally:
+                ctx.set_exact_below(256)
+
+        def default():  # the route the call takes by default
+            last["default"] = ctx.verify_signed_msgs(ks, signer, msgs, sigs)
+
+        def composed():
+            H = ctx.hash_g2_batch(msgs)
+            last["old"] = ctx.verify_sigs(item_pks, H, sigs)
+
+        for _ in range(max(warmup, 1)):
+            grouped()
+            default()
+            composed()
+        if last["new"].tolist() != np.asarray(last["old"]).tolist() or \
+                last["default"].tolist() != last["new"].tolist():
+            raise SystemExit("sv: hbtc_verify_signed_msgs differs from the composed calls at %d bytes" % size)
+        if int((last["new"] != N.ACCEPT).sum()) != 1 or last["new"][n_items // 2] != N.REJECT:
+            raise SystemExit("sv: expected exactly one rejected item")
+        times = {"grouped": [], "verify_signed_msgs": [], "composed": []}
+        for _ in range(steps):  # interleaved: every repeat runs the paths back to back
+            for name, fn in (("grouped", grouped), ("verify_signed_msgs", default), ("composed", composed)):
+                t1 = time.perf_counter()
+                fn()
+                times[name].append((time.perf_counter() - t1) * 1e3)
+        r = {name: stat(ts) for name, ts in times.items()}
+        r["composed_over_grouped"] = round(r["composed"]["median_ms"] / r["grouped"]["median_ms"], 3)
+        r["composed_over_default"] = round(r["composed"]["median_ms"] / r["verify_signed_msgs"]["median_ms"], 3)
+        r["spans"] = spans(grouped)
+        r["spans_default"] = spans(default)
+        r["spans_composed"] = spans(composed)
+        r["statuses_equal"] = True
+        out["msg_%dB" % size] = r
+    ctx.keyset_free(ks)
+    a = out["msg_128B"]
+    res = {
+        "metric": "signed messages verified/sec (hbtc_verify_signed_msgs, 128-byte messages)",
+        "value": round(n_items / (a["verify_signed_msgs"]["median_ms"] * 1e-3), 1), "unit": "items/s",
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "higher_is_better": True,
+        "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (%d signers, %d items spread evenly and interleaved, one rejected item); host "
+                "buffers (PCIe-inclusive), Python marshalling included" % (n_signers, n_items),
+        "config": {"workload": "sv: DynamicHoneyBadger's signed votes / key-gen messages, grouped by signer, "
+                               "against hbtc_hash_g2_batch_gpu + hbtc_verify_sigs on the same inputs",
+                   "signers": n_signers, "items": n_items,
+                   "mode": "rlc" if ctx_mode[0] == N.MODE_RLC else "per_share"},
+    }
+    res.update(out)
+    return res
+
+
 def bench_broadcast(ctx, n, value_bytes, steps, warmup):
     """bc: one node's Reliable Broadcast work for an epoch of n proposers (see the docstring)."""
     from hbbft_amd import broadcast as G
@@ -1282,6 +1392,8 @@ def main():
                 out = bench_threshold_decrypt(ctx, args.nodes, args.td_bytes, steps, warmup, args.corrupt)
             elif c == "own":
                 out = bench_own_shares(ctx, args.td_bytes, steps, warmup)
+            elif c == "sv":
+                out = bench_signed_msgs(ctx, steps, warmup)
             elif c == "kg":
                 out = bench_keygen(ctx, args.nodes, steps, warmup, parent=args.kg_parent)
             elif c == "c5p":

@@ -2,7 +2,8 @@
 
 The compute path is the HIP library ``hbbft_amd/libhbtc.so`` (gfx950 kernels behind the C ABI
 of ``include/hbtc.h``); ``hbbft_amd._native`` binds it with ctypes; ``protocol`` (Coin,
-ThresholdDecryption), ``skg`` (SyncKeyGen) and ``broadcast`` (Reliable Broadcast coding) mirror
+ThresholdDecryption), ``skg`` (SyncKeyGen), ``dhb`` (DynamicHoneyBadger's signed votes and key-gen
+messages) and ``broadcast`` (Reliable Broadcast coding) mirror
 the hbbft call sites as batch queues; ``shard`` plans multi-GPU splits; ``wire`` restates the
 bincode framing.  Nothing here falls back to the CPU: if the library is missing, calls raise
 ``NativeUnavailable``.

@@ -121,6 +121,7 @@ SIGNATURES = {
     "hbtc_encrypt": (_I32, [_P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "hbtc_decrypt_shares": (_I32, [_P, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hbtc_sign_shares": (_I32, [_P, _U32, _P, _P, _P, _P, _P]),
+    "hbtc_verify_signed_msgs": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P]),
     "hbtc_fr_poly_eval": (_I32, [_P, _U32, _U32, _P, _U32, _P, _P]),
     "hbtc_skg_generate": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "hbtc_unframe_points_dev": (_I32, [_P, _U32, _U32, _P, _P]),
@@ -876,6 +877,23 @@ class Context:
         hb = H.tobytes() if want_H else None
         return ([sb[96 * i:96 * i + 96] for i in range(n)],
                 [hb[96 * i:96 * i + 96] for i in range(n)] if want_H else None)
+
+    def verify_signed_msgs(self, keyset_id, signer, msgs, sigs):
+        """PublicKey::verify(sig_i, msg_i) under key signer[i] of the key set (the validators'
+        individual public keys, a candidate's appended), hashed and grouped by signer on the GPU:
+        int32 statuses, equal to verify_sigs(pk[signer[i]], hash_g2(msg_i), sig_i)."""
+        buf, off = _msg_batch(msgs)
+        n = off.size - 1
+        if n == 0:
+            return np.zeros(0, np.int32)
+        who = np.ascontiguousarray(signer, np.uint32)
+        sb = _join(sigs, 96)
+        if who.size != n or sb.size != 96 * n:
+            raise ValueError("one signer and one 96-byte signature per message")
+        st = np.zeros(n, np.int32)
+        self._check(self.lib.hbtc_verify_signed_msgs(self.h, keyset_id, n, _ptr(who), _ptr(buf), _ptr(off),
+                                                     _ptr(sb), _ptr(st)), "hbtc_verify_signed_msgs")
+        return st
 
     # ---- Fr polynomials
     def fr_poly_eval(self, coeffs, xs):

@@ -54,6 +54,7 @@ struct Keyset {
   uint32_t calls = 0;            // RLC verification calls on this key set
   uint32_t n = 0;
   G1A* master = nullptr;         // hbtc_keyset_set_master: the decoded master public key
+  uint8_t* c48 = nullptr;        // the keys compressed, built at the first hbtc_verify_signed_msgs that needs them
 };
 
 constexpr uint32_t FACT_N = 65535;  // factorial tables of the Lagrange coefficients (node indices < FACT_N)
@@ -1659,6 +1660,7 @@ void keyset_release(Keyset& ks) {
   (void)hipFree(ks.last_bad);
   (void)hipFree(ks.rejects);
   (void)hipFree(ks.master);
+  (void)hipFree(ks.c48);
   ks = Keyset();
 }
 
@@ -1822,6 +1824,7 @@ void hbtc_ctx_destroy(hbtc_ctx* c) {
     (void)hipFree(kv.second.last_bad);
     (void)hipFree(kv.second.rejects);
     (void)hipFree(kv.second.master);
+    (void)hipFree(kv.second.c48);
   }
   for (Span& sp : c->spans) {
     (void)hipEventDestroy(sp.a);
@@ -2217,15 +2220,18 @@ int hbtc_coin_decide(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uin
 // cooperative leaf checks.  Four dependent launches for c1's master signature instead of the
 // pair batch's item pass, line tables, Miller partials and final exponentiation.  Statuses as
 // the pair check's: an A, Q or W that fails to decode is the item's DECODE_ERR.
+// (pre_a / pre_st: the A_i already decoded with their statuses -- key-set entries gathered per
+// item by hbtc_verify_signed_msgs -- instead of d_a.)
 int pb_small_exact_chunk(hbtc_ctx* c, uint32_t n, const uint8_t* d_a, const uint8_t* d_q,
-                         const uint8_t* d_w, int32_t* d_status, G1A* d_adec) {
+                         const uint8_t* d_w, int32_t* d_status, G1A* d_adec, const G1A* pre_a = nullptr,
+                         const int32_t* pre_st = nullptr) {
   std::vector<uint32_t> offsets(n + 1), idx(n);
   for (uint32_t i = 0; i <= n; ++i) offsets[i] = i;
   for (uint32_t i = 0; i < n; ++i) idx[i] = i;
-  G1A* A = d_adec;
-  int32_t* a_st;
+  G1A* A = pre_a ? const_cast<G1A*>(pre_a) : d_adec;
+  int32_t* a_st = const_cast<int32_t*>(pre_st);
   if (!A) HB_TRY(wst(c, "pbx.a", n, &A));
-  HB_TRY(wst(c, "pbx.ast", n, &a_st));
+  if (!pre_a) HB_TRY(wst(c, "pbx.ast", n, &a_st));
   void* p;
   HB_TRY(stage_upload(c, "pbx.idx", idx.data(), (size_t)4 * n, c->stream, &p));
   const uint32_t* d_idx = static_cast<const uint32_t*>(p);
@@ -2248,7 +2254,7 @@ int pb_small_exact_chunk(hbtc_ctx* c, uint32_t n, const uint8_t* d_a, const uint
   HB_TRY(wst(c, "pbx.counters", 2, &counters));
   HB_TRY(wst(c, "pbx.leaves", (size_t)2 * n, &leaves));
   HB_CHECK(c, launch_zero_u32(c->stream, counters, 2));
-  HB_TRY(timed(c, "pb_decode", [&] { return launch_g1_decode(c->stream, d_a, n, A, a_st); }));
+  if (!pre_a) HB_TRY(timed(c, "pb_decode", [&] { return launch_g1_decode(c->stream, d_a, n, A, a_st); }));
   RlcKey key{};  // no group sums (Suspects.all): the scalars and the pk table are never read
   key.bits = c->rlc_bits;
   const Suspects sus{nullptr, 0, counters, leaves, 1};
@@ -2283,12 +2289,14 @@ int pb_small_exact_chunk(hbtc_ctx* c, uint32_t n, const uint8_t* d_a, const uint
 // pb_small_exact over any n: chunks of PBX_CHUNK items (19.6 KB of line tables per item).
 constexpr uint32_t PBX_CHUNK = 1u << 15;
 int pb_small_exact(hbtc_ctx* c, uint32_t n, const uint8_t* d_a, const uint8_t* d_q,
-                   const uint8_t* d_w, int32_t* d_status, G1A* d_adec) {
-  if (!d_a) return fail(c, HBTC_ERR_ARG, "pair checks need their G1 arguments");
+                   const uint8_t* d_w, int32_t* d_status, G1A* d_adec, const G1A* pre_a = nullptr,
+                   const int32_t* pre_st = nullptr) {
+  if (!d_a && !pre_a) return fail(c, HBTC_ERR_ARG, "pair checks need their G1 arguments");
   for (uint32_t base = 0; base < n; base += PBX_CHUNK) {
     const uint32_t m = std::min(PBX_CHUNK, n - base);
-    HB_TRY(pb_small_exact_chunk(c, m, d_a + (size_t)48 * base, d_q + (size_t)96 * base,
-                                d_w + (size_t)96 * base, d_status + base, d_adec ? d_adec + base : nullptr));
+    HB_TRY(pb_small_exact_chunk(c, m, pre_a ? nullptr : d_a + (size_t)48 * base, d_q + (size_t)96 * base,
+                                d_w + (size_t)96 * base, d_status + base, d_adec ? d_adec + base : nullptr,
+                                pre_a ? pre_a + base : nullptr, pre_a ? pre_st + base : nullptr));
   }
   return HBTC_OK;
 }
@@ -3605,6 +3613,330 @@ int hbtc_sign_shares(hbtc_ctx* c, uint32_t n, const uint8_t* sk_le32, const uint
       if (out_H_c96) memcpy(out_H_c96 + 96 * (size_t)redo[j], H.data() + 96 * (size_t)j, 96);
     }
   }
+  return HBTC_OK;
+}
+
+// ---- hbtc.h hbtc_verify_signed_msgs (kernels: hbtc_sv.hip)
+// The call's device arrays.  The items are sorted by signer (signers past the key set last):
+// d_signer, d_perm (the item's place in the caller's order), d_sig and d_st are in sorted order,
+// d_cand (the hash candidates) in the caller's.
+struct SvCall {
+  const uint32_t* d_signer = nullptr;
+  const uint32_t* d_perm = nullptr;
+  const uint8_t* d_sig = nullptr;
+  const G2A* d_cand = nullptr;
+  int32_t* d_st = nullptr;
+  const uint32_t* perm = nullptr;  // host copies, for the redrawn hashes
+  const uint8_t* msgs = nullptr;
+  const uint32_t* offsets = nullptr;
+};
+
+// The composed route for the `cnt` items d_list names (positions from `base` in sorted order):
+// the signers' keys gathered per item, H compressed from the candidates (launch_g2_clear_cofactor;
+// a flagged [h2] cand = O item is hashed on the host, as in hash_batch_gpu), then the exact pair
+// checks on the decoded keys, or (pair_batch) hbtc_verify_sigs' pair batch on the compressed
+// ones; the verdicts scattered back.
+static int sv_exact_list(hbtc_ctx* c, Keyset& ks, const SvCall& sv, uint32_t base, uint32_t cnt,
+                         const uint32_t* d_list, bool pair_batch = false) {
+  if (cnt == 0) return HBTC_OK;
+  G1A* ga;
+  G2A* gcand;
+  int32_t *gast, *gst, *gflag;
+  uint8_t *gsig, *gq;
+  HB_TRY(wst(c, "svx.a", cnt, &ga));
+  HB_TRY(wst(c, "svx.ast", cnt, &gast));
+  HB_TRY(wst(c, "svx.cand", cnt, &gcand));
+  HB_TRY(wst(c, "svx.sig", (size_t)96 * cnt, &gsig));
+  HB_TRY(wst(c, "svx.q", (size_t)96 * cnt, &gq));
+  HB_TRY(wst(c, "svx.st", cnt, &gst));
+  HB_TRY(wst(c, "svx.flag", cnt, &gflag));
+  HB_CHECK(c, launch_sv_gather(c->stream, cnt, d_list, sv.d_signer + base, sv.d_perm + base, sv.d_cand,
+                               sv.d_sig + (size_t)96 * base, ks.pk, ks.st, ks.n, ga, gast, gcand, gsig));
+  HB_TRY(timed(c, "hash", [&] { return launch_g2_clear_cofactor(c->stream, cnt, gcand, gq, gflag); }));
+  std::vector<int32_t> flag(cnt);
+  std::vector<uint32_t> list(cnt);
+  HB_TRY(download(c, flag.data(), gflag, (size_t)4 * cnt));
+  HB_TRY(download(c, list.data(), d_list, (size_t)4 * cnt));
+  HB_CHECK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t g = 0; g < cnt; ++g)  // [h2] P = O: G2::rand draws again (host, exact)
+    if (flag[g]) {
+      const uint32_t i = sv.perm[base + list[g]];
+      uint8_t h[96];
+      hash_g2_c96(sv.msgs + sv.offsets[i], sv.offsets[i + 1] - sv.offsets[i], h);
+      HB_CHECK(c, hipMemcpy(gq + 96 * (size_t)g, h, 96, hipMemcpyHostToDevice));
+    }
+  if (pair_batch) {
+    // the composed calls' own route: the pair batch of hbtc_verify_sigs, which decodes its keys
+    if (!ks.c48) {
+      HB_CHECK(c, hipMalloc(&ks.c48, (size_t)48 * ks.n));
+      HB_CHECK(c, launch_sv_pk_c48(c->stream, ks.n, ks.pk, ks.st, ks.c48));
+    }
+    uint8_t* gc48;
+    HB_TRY(wst(c, "svx.c48", (size_t)48 * cnt, &gc48));
+    HB_CHECK(c, launch_sv_gather_c48(c->stream, cnt, d_list, sv.d_signer + base, ks.c48, ks.n, gc48));
+    HB_TRY(pb_verify_dev(c, cnt, gc48, gq, true, gsig, gst));
+  } else {
+    HB_TRY(pb_small_exact(c, cnt, nullptr, gq, gsig, gst, nullptr, ga, gast));
+  }
+  HB_CHECK(c, launch_pb_scatter(c->stream, cnt, d_list, gst, sv.d_st + base));
+  return HBTC_OK;
+}
+
+// The signer-level checks of one round: the slots as the items of a pair batch with pre-scaled
+// input (k_sv_signers), their line tables and Miller partials, then either the 64-slot tiles and
+// the 8-slot sub-tiles of failing tiles (spread = false), or, with one signer per sub-tile
+// (spread = true: the signers of a failing sub-tile, re-laid at slots 8 k), the sub-tile checks
+// alone.  The slots still PENDING afterwards are listed in *slist, their number in counters[1].
+static int sv_checks(hbtc_ctx* c, const Keyset& ks, uint32_t n_slots, const uint32_t* d_slot_signer,
+                     const uint32_t* d_slot_node, const G2J* nodeS, const G2J* nodeT, uint32_t stride,
+                     bool spread, uint32_t* counters, uint32_t** slist) {
+  const uint32_t T = (n_slots + 63) / 64;
+  G1A* rA;
+  G2A* qdec;
+  int32_t* sst;
+  SigTileSums* ssums;
+  Fq2 *qtab, *wtab, *fbuf;
+  uint32_t *winf, *tlist;
+  HB_TRY(wst(c, "sv.ra", n_slots, &rA));
+  HB_TRY(wst(c, "sv.qdec", n_slots, &qdec));
+  HB_TRY(wst(c, "sv.sst", n_slots, &sst));
+  HB_TRY(wst(c, "sv.ssums", T, &ssums));
+  HB_TRY(wst(c, "sv.qtab", (size_t)n_slots * PLINES_FQ2, &qtab));
+  HB_TRY(wst(c, "sv.wtab", (size_t)8 * T * PLINES_FQ2, &wtab));
+  HB_TRY(wst(c, "sv.winf", (size_t)8 * T, &winf));
+  HB_TRY(wst(c, "sv.fbuf", (size_t)8 * T * 6, &fbuf));
+  HB_TRY(wst(c, "sv.tlist", (size_t)T + 1, &tlist));
+  HB_TRY(wst(c, "sv.slist", n_slots, slist));
+  const uint32_t* sub_count = counters;
+  if (spread) {  // every tile is "listed": its sub-tiles are the checks
+    std::vector<uint32_t> all(T + 1);
+    all[0] = T;
+    for (uint32_t t = 0; t < T; ++t) all[t + 1] = t;
+    void* p;
+    HB_TRY(stage_upload(c, "sv.tlist", all.data(), (size_t)4 * (T + 1), c->stream, &p));
+    tlist = static_cast<uint32_t*>(p) + 1;
+    sub_count = static_cast<uint32_t*>(p);
+  }
+  uint32_t* out = *slist;
+  return timed(c, "sv_checks", [&] {
+    hipError_t e = launch_sv_signers(c->stream, n_slots, d_slot_signer, d_slot_node, nodeS, nodeT, stride,
+                                     ks.pk, ks.st, rA, qdec, sst, ssums);
+    if (e != hipSuccess) return e;
+    if ((e = launch_pb_lines(c->stream, n_slots, qdec, sst, qtab)) != hipSuccess) return e;
+    if ((e = launch_pb_ml(c->stream, n_slots, rA, qtab, sst, fbuf)) != hipSuccess) return e;
+    if (!spread) {
+      e = launch_plines(c->stream, 3, T, 0, nullptr, nullptr, nullptr, ssums, nullptr, wtab, winf);
+      if (e != hipSuccess) return e;
+      e = launch_pb_fe(c->stream, 0, T, n_slots, T, nullptr, nullptr, fbuf, wtab, winf, sst, counters, tlist);
+      if (e != hipSuccess) return e;
+    }
+    e = launch_plines(c->stream, 4, 8 * T, 0, sub_count, tlist, nullptr, ssums, nullptr, wtab, winf);
+    if (e != hipSuccess) return e;
+    return launch_pb_fe(c->stream, 1, 8 * T, n_slots, 0, sub_count, tlist, fbuf, wtab, winf, sst,
+                        counters + 1, out);
+  });
+}
+
+// One chunk of the grouped route: items [base, base + m) in sorted order; start[b] is the first
+// sorted position of signer b's items (b = K: the signers past the key set), start[K + 1] = n.
+static int sv_chunk(hbtc_ctx* c, Keyset& ks, const SvCall& sv, const std::vector<uint32_t>& start,
+                    uint32_t base, uint32_t m) {
+  const uint32_t K = ks.n;
+  constexpr uint32_t SUM_STRIDE = sizeof(SvTileSums) / sizeof(G2J);
+  struct Run {
+    uint32_t signer, first, count;  // the signer's nodes at the current level
+  };
+  std::vector<Tile> tiles;
+  std::vector<Run> runs;  // the key-set signers with items in this chunk
+  for (uint32_t b = 0; b <= K; ++b) {
+    const uint32_t lo = std::max(start[b], base), hi = std::min(start[b + 1], base + m);
+    if (lo >= hi) continue;
+    if (b < K) runs.push_back(Run{b, (uint32_t)tiles.size(), (hi - lo + TILE_ITEMS - 1) / TILE_ITEMS});
+    for (uint32_t s = lo; s < hi; s += TILE_ITEMS) tiles.push_back(Tile{b, s - base, std::min(TILE_ITEMS, hi - s), 0});
+  }
+  const uint32_t n_tiles = (uint32_t)tiles.size();
+  // the passes of the signers' trees: groups of at most 64 consecutive nodes of one signer
+  std::vector<Tile> groups;
+  std::vector<std::pair<uint32_t, uint32_t>> passes;  // (first group, groups) per pass
+  for (;;) {
+    uint32_t most = 0;
+    for (const Run& r : runs) most = std::max(most, r.count);
+    if (most <= 1) break;
+    const uint32_t g0 = (uint32_t)groups.size();
+    for (Run& r : runs) {
+      const uint32_t first = (uint32_t)groups.size() - g0;
+      for (uint32_t s = 0; s < r.count; s += 64) groups.push_back(Tile{r.signer, r.first + s, std::min(64u, r.count - s), 0});
+      r.first = first;
+      r.count = (uint32_t)groups.size() - g0 - first;
+    }
+    passes.push_back({g0, (uint32_t)groups.size() - g0});
+  }
+  void* p;
+  HB_TRY(stage_upload(c, "sv.tiles", tiles.data(), tiles.size() * sizeof(Tile), c->stream, &p));
+  const Tile* d_tiles = static_cast<const Tile*>(p);
+  HB_TRY(stage_upload(c, "sv.groups", groups.data(), groups.size() * sizeof(Tile), c->stream, &p));
+  const Tile* d_groups = static_cast<const Tile*>(p);
+  const uint32_t n_slots = (uint32_t)runs.size();
+  std::vector<uint32_t> slots(2 * (size_t)n_slots);
+  for (uint32_t s = 0; s < n_slots; ++s) {
+    slots[s] = runs[s].signer;
+    slots[n_slots + s] = runs[s].first;
+  }
+  HB_TRY(stage_upload(c, "sv.slots", slots.data(), slots.size() * 4, c->stream, &p));
+  const uint32_t* d_slots = static_cast<const uint32_t*>(p);
+  G2A* dec;
+  SvTileSums* sums;
+  G2J* nodes[2];
+  uint32_t* counters;
+  const uint32_t node_cap = passes.empty() ? 0 : passes[0].second;
+  HB_TRY(wst(c, "sv.dec", m, &dec));
+  HB_TRY(wst(c, "sv.sums", n_tiles, &sums));
+  HB_TRY(wst(c, "sv.nodes0", (size_t)2 * node_cap, &nodes[0]));
+  HB_TRY(wst(c, "sv.nodes1", (size_t)2 * node_cap, &nodes[1]));
+  HB_TRY(wst(c, "sv.counters", 4, &counters));
+  const uint32_t* d_signer = sv.d_signer + base;
+  int32_t* st = sv.d_st + base;
+  RlcKey key;
+  for (int i = 0; i < 8; ++i) key.k[i] = c->rd();
+  key.bits = c->rlc_bits;
+  HB_CHECK(c, launch_zero_u32(c->stream, counters, 4));
+  HB_TRY(timed(c, "sv_items", [&] {
+    const hipError_t e = launch_sig_decode_only(c->stream, n_tiles, d_tiles, d_signer,
+                                                sv.d_sig + (size_t)96 * base, ks.st, K, dec, st);
+    if (e != hipSuccess) return e;
+    return launch_sv_items(c->stream, n_tiles, d_tiles, d_signer, sv.d_perm + base, sv.d_cand, dec, ks.pk,
+                           ks.st, K, key, sums, st, counters + 2);
+  }));
+  const G2J *nodeS = &sums[0].S[8], *nodeT = &sums[0].T[8];
+  uint32_t stride = SUM_STRIDE;
+  for (size_t k = 0; k < passes.size(); ++k) {
+    G2J* out = nodes[k & 1];
+    HB_TRY(timed(c, "sv_sums", [&] {
+      return launch_sv_sums(c->stream, passes[k].second, d_groups + passes[k].first, nodeS, nodeT, stride, out,
+                            out + node_cap);
+    }));
+    nodeS = out;
+    nodeT = out + node_cap;
+    stride = 1;
+  }
+  uint32_t* slist;
+  HB_TRY(sv_checks(c, ks, n_slots, d_slots, d_slots + n_slots, nodeS, nodeT, stride, false, counters, &slist));
+  uint32_t cnt[4];
+  HB_TRY(download(c, cnt, counters, 16));
+  HB_CHECK(c, hipStreamSynchronize(c->stream));
+  if (cnt[1] == 0 && cnt[2] == 0) {  // every signer passed, nothing for the exact route
+    HB_CHECK(c, launch_sv_finish(c->stream, m, d_signer, nullptr, st, nullptr, nullptr));
+    return HBTC_OK;
+  }
+  if (cnt[1] > n_slots) return fail(c, HBTC_ERR_DEVICE, "signed messages: signer count past the slots");
+  std::vector<uint32_t> sbad(K, 0);
+  if (cnt[1]) {
+    // the signers of the failing sub-tiles, one per sub-tile: one check per signer
+    std::vector<uint32_t> failing(cnt[1]);
+    HB_TRY(download(c, failing.data(), slist, (size_t)4 * cnt[1]));
+    HB_CHECK(c, hipStreamSynchronize(c->stream));
+    const uint32_t n2 = 8 * cnt[1];
+    std::vector<uint32_t> slots2(2 * (size_t)n2, SV_NONE);
+    for (uint32_t k = 0; k < cnt[1]; ++k) {
+      if (failing[k] >= n_slots) return fail(c, HBTC_ERR_DEVICE, "signed messages: bad signer slot");
+      slots2[8 * k] = runs[failing[k]].signer;
+      slots2[n2 + 8 * k] = runs[failing[k]].first;
+    }
+    HB_TRY(stage_upload(c, "sv.slots", slots2.data(), slots2.size() * 4, c->stream, &p));
+    const uint32_t* d_slots2 = static_cast<const uint32_t*>(p);
+    HB_CHECK(c, launch_zero_u32(c->stream, counters + 1, 1));
+    HB_TRY(sv_checks(c, ks, n2, d_slots2, d_slots2 + n2, nodeS, nodeT, stride, true, counters, &slist));
+    uint32_t bad = 0;
+    HB_TRY(download(c, &bad, counters + 1, 4));
+    HB_CHECK(c, hipStreamSynchronize(c->stream));
+    if (bad > cnt[1]) return fail(c, HBTC_ERR_DEVICE, "signed messages: failing signers past the list");
+    std::vector<uint32_t> q(bad);
+    HB_TRY(download(c, q.data(), slist, (size_t)4 * bad));
+    HB_CHECK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < bad; ++k) {
+      if (q[k] >= n2 || slots2[q[k]] == SV_NONE) return fail(c, HBTC_ERR_DEVICE, "signed messages: bad signer slot");
+      sbad[slots2[q[k]]] = 1;
+    }
+  }
+  HB_TRY(stage_upload(c, "sv.sbad", sbad.data(), (size_t)4 * K, c->stream, &p));
+  uint32_t* leaves;
+  HB_TRY(wst(c, "sv.leaves", m, &leaves));
+  HB_CHECK(c, launch_sv_finish(c->stream, m, d_signer, static_cast<const uint32_t*>(p), st, counters + 3, leaves));
+  uint32_t n_leaves = 0;
+  HB_TRY(download(c, &n_leaves, counters + 3, 4));
+  HB_CHECK(c, hipStreamSynchronize(c->stream));
+  if (n_leaves > m) return fail(c, HBTC_ERR_DEVICE, "signed messages: leaf count past the chunk");
+  return sv_exact_list(c, ks, sv, base, n_leaves, leaves);
+}
+
+int hbtc_verify_signed_msgs(hbtc_ctx* c, uint32_t keyset_id, uint32_t n, const uint32_t* signer,
+                            const uint8_t* msgs, const uint32_t* offsets, const uint8_t* sig_c96,
+                            int32_t* status) {
+  if (!c) return HBTC_ERR_ARG;
+  if (n == 0) return HBTC_OK;
+  if (!signer || !offsets || !sig_c96 || !status || (offsets[n] && !msgs) || !hash_offsets_ok(n, offsets))
+    return HBTC_ERR_ARG;
+  Guard g(c);
+  Keyset* ks;
+  HB_TRY(get_keyset(c, keyset_id, &ks));
+  const uint32_t K = ks->n;
+  // counting sort by signer; the signers past the key set share the last bucket
+  std::vector<uint32_t> start(K + 2, 0), perm(n), sorted_signer(n);
+  for (uint32_t i = 0; i < n; ++i) ++start[std::min(signer[i], K) + 1];
+  for (uint32_t b = 0; b <= K; ++b) start[b + 1] += start[b];
+  {
+    std::vector<uint32_t> next(start.begin(), start.end() - 1);
+    for (uint32_t i = 0; i < n; ++i) perm[next[std::min(signer[i], K)]++] = i;
+  }
+  std::vector<uint8_t> sorted_sig((size_t)96 * n);
+  for (uint32_t pos = 0; pos < n; ++pos) {
+    sorted_signer[pos] = signer[perm[pos]];
+    memcpy(sorted_sig.data() + 96 * (size_t)pos, sig_c96 + 96 * (size_t)perm[pos], 96);
+  }
+  HB_TRY(sync(c));
+  void *d_msgs, *d_off, *d_signer, *d_perm, *d_sig;
+  G2A* d_cand;
+  SvCall sv;
+  HB_TRY(upload_msgs(c, msgs, offsets[n], &d_msgs));
+  HB_TRY(upload(c, "hash.off", offsets, (size_t)4 * (n + 1), &d_off));
+  HB_TRY(upload(c, "sv.signer", sorted_signer.data(), (size_t)4 * n, &d_signer));
+  HB_TRY(upload(c, "sv.perm", perm.data(), (size_t)4 * n, &d_perm));
+  HB_TRY(upload(c, "sv.sig", sorted_sig.data(), (size_t)96 * n, &d_sig));
+  HB_TRY(wst(c, "hash.cand", n, &d_cand));
+  HB_TRY(wst(c, "sv.st", n, &sv.d_st));
+  sv.d_signer = static_cast<const uint32_t*>(d_signer);
+  sv.d_perm = static_cast<const uint32_t*>(d_perm);
+  sv.d_sig = static_cast<const uint8_t*>(d_sig);
+  sv.d_cand = d_cand;
+  sv.perm = perm.data();
+  sv.msgs = msgs;
+  sv.offsets = offsets;
+  HB_TRY(timed(c, "hash", [&] {
+    return launch_hash_cand(c->stream, n, nullptr, (const uint8_t*)d_msgs, (const uint32_t*)d_off, d_cand);
+  }));
+  const uint32_t n_known = start[K];
+  // Routes (equal decisions): per-share mode and calls below hbtc_set_exact_below check every item
+  // exactly; hbtc_set_exact_below(ctx, 0) ("always batch") selects the grouped path; every other
+  // call takes the composed route, hash + hbtc_verify_sigs' pair batch, which measured faster than
+  // the grouped path at 1,000 signers x 64 k items (DESIGN.md §5 "Signed messages")
+  const bool exact = c->verify_mode == HBTC_MODE_PER_SHARE || n < c->exact_below;
+  const bool composed = exact || c->exact_below != 0;
+  if (composed) {
+    // every item of a key-set signer (sorted positions [0, n_known))
+    std::vector<uint32_t> all(n_known);
+    for (uint32_t i = 0; i < n_known; ++i) all[i] = i;
+    void* d_all;
+    HB_TRY(upload(c, "sv.leaves", all.data(), (size_t)4 * n_known, &d_all));
+    HB_TRY(sv_exact_list(c, *ks, sv, 0, n_known, static_cast<const uint32_t*>(d_all), !exact));
+  } else {
+    for (uint32_t base = 0; base < n; base += c->pb_chunk)
+      HB_TRY(sv_chunk(c, *ks, sv, start, base, std::min(c->pb_chunk, n - base)));
+  }
+  std::vector<int32_t> st(n);
+  HB_TRY(download(c, st.data(), sv.d_st, (size_t)4 * n));
+  HB_TRY(sync(c));
+  for (uint32_t pos = 0; pos < n; ++pos)
+    status[perm[pos]] = composed && pos >= n_known ? HBTC_UNKNOWN_SENDER : st[pos];
   return HBTC_OK;
 }
 

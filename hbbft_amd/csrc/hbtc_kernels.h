@@ -258,6 +258,52 @@ hipError_t launch_pb_fe(hipStream_t s, int level, uint32_t max_groups, uint32_t 
                         uint32_t n_direct, const uint32_t* n_listed, const uint32_t* list,
                         const Fq2* fbuf, const Fq2* wtab, const uint32_t* winf, int32_t* status,
                         uint32_t* out_count, uint32_t* out_list);
+// ---- signed messages grouped by signer (hbtc_sv.hip; checks: the pair batch's, above)
+// Sums of one tile of at most 64 items of ONE signer: S = sum r_i H_i, T = sum r_i sigma_i
+// ([8] the tile; [0..7] and the weighted SW / TW are rlc_reduce_g2p's other outputs, unused).
+struct SvTileSums {
+  G2J S[9];
+  G2J SW[9];
+  G2J T[9];
+  G2J TW[9];
+};
+constexpr uint32_t SV_NONE = 0xffffffffu;  // an empty signer slot
+// the decode half of the SignatureShare item pass alone (hbtc_sig.hip): sigma_i of tile item i
+// decoded with the psi subgroup test into dec, DECODE_ERR / RLC_PENDING into status
+hipError_t launch_sig_decode_only(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
+                                  const uint8_t* sigs, const int32_t* pk_status, uint32_t n_pk, G2A* dec,
+                                  int32_t* status);
+// items sorted by signer (tiles never cross a signer): H = [h2] cand[perm[i]], r_i H_i and
+// r_i sigma_i on lane pairs, the tile sums; statuses PENDING / DECODE_ERR / UNKNOWN_SENDER /
+// RLC_LEAF (exact route; counted in *leaf_items)
+hipError_t launch_sv_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* signer,
+                           const uint32_t* perm, const G2A* cand, const G2A* dec, const G1A* pk,
+                           const int32_t* pk_status, uint32_t n_pk, RlcKey key, SvTileSums* sums,
+                           int32_t* status, uint32_t* leaf_items);
+// one pass of the signers' trees: group g (nodes [first, first + count) of one signer, at most 64)
+// -> outS[g], outT[g]; input node k at inS / inT[k * stride]
+hipError_t launch_sv_sums(hipStream_t s, uint32_t n_groups, const Tile* groups, const G2J* inS, const G2J* inT,
+                          uint32_t stride, G2J* outS, G2J* outT);
+// the signers as pre-scaled pair-batch items: slot s = signer slot_signer[s] (SV_NONE: empty) with
+// sums at node slot_node[s] -> rA = P_j, Qdec = affine S_j, sst = PENDING / ACCEPT (skipped),
+// sums[tile].S = the 8- and 64-slot sums of T_j
+hipError_t launch_sv_signers(hipStream_t s, uint32_t n_slots, const uint32_t* slot_signer,
+                             const uint32_t* slot_node, const G2J* nodeS, const G2J* nodeT, uint32_t stride,
+                             const G1A* pk, const int32_t* pk_status, G1A* rA, G2A* Qdec, int32_t* sst,
+                             SigTileSums* sums);
+// PENDING items: ACCEPT, or RLC_LEAF where sbad[signer] (null: none); RLC_LEAF items -> list
+// (null: not listed)
+hipError_t launch_sv_finish(hipStream_t s, uint32_t n, const uint32_t* signer, const uint32_t* sbad,
+                            int32_t* status, uint32_t* count, uint32_t* list);
+hipError_t launch_sv_gather(hipStream_t s, uint32_t n, const uint32_t* list, const uint32_t* signer,
+                            const uint32_t* perm, const G2A* cand, const uint8_t* sig, const G1A* pk,
+                            const int32_t* pk_status, uint32_t n_pk, G1A* ga, int32_t* gast, G2A* gcand,
+                            uint8_t* gsig);
+// the key set's keys compressed (48 zero bytes for a key that failed to load), and the listed
+// items' signers' compressed keys: the G1 arguments of the composed pair-batch route
+hipError_t launch_sv_pk_c48(hipStream_t s, uint32_t n, const G1A* pk, const int32_t* pk_status, uint8_t* out_c48);
+hipError_t launch_sv_gather_c48(hipStream_t s, uint32_t n, const uint32_t* list, const uint32_t* signer,
+                                const uint8_t* pk_c48, uint32_t n_pk, uint8_t* gc48);
 // k_i P_i; base_stride / scalar_stride 0 = one base / scalar for every item
 hipError_t launch_point_mul(hipStream_t s, int group, uint32_t n, const uint8_t* base,
                             uint32_t base_stride, const uint8_t* scalars, uint32_t scalar_stride,

@@ -16,6 +16,7 @@
 // step) and evaluated at the fixed point -G1 by the cooperative check (gt6.h miller2_t<true>).
 #include "gt6.h"
 #include "pair.h"
+#include "pair_tree.h"
 #include "rlc_common.h"
 
 namespace hbtc {
@@ -276,15 +277,6 @@ __global__ void __launch_bounds__(64, 1) k_sig_items(
 #ifndef HBTC_SIGP_WAVES
 #define HBTC_SIGP_WAVES 2  // k_sig_items_pair: minimum waves per SIMD of the register allocation
 #endif
-// The wave-local form of a __syncthreads between LDS writes and reads of ONE wave: a wave's LDS
-// operations execute in order, so only the compiler's reordering and the outstanding counters
-// need fencing.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // r pk_i of the x-adic scalar on a lane pair: lane e takes digits e and e + 2 (the pk window of
 // digit e, then the phi window of digit e + 2: the beta product is on the same iteration for
 // both lanes), 8 of the 16 mixed additions; the pair's halves are then added (both lanes hold
@@ -323,20 +315,8 @@ __device__ __forceinline__ void rlc_pk_mul_x_pair(G1J& r, const PtXY* __restrict
   jac_add(r, r, o);
 }
 
-// LDS layouts of the two reductions: word w of item m's G2 point component e at
-// w * 128 + 2 m + e (36 words), of its G1 point at w * 64 + m -- a wave's stores are conflict-free.
-__device__ __forceinline__ void g2p_lds_put(uint32_t* lds, uint32_t m, const G2Jp& a) {
-  const uint32_t o = 2 * m + (pair_odd() ? 1u : 0u);
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(&a);
-#pragma unroll
-  for (int w = 0; w < 36; ++w) lds[w * 128 + o] = src[w];
-}
-__device__ __forceinline__ void g2p_lds_get(G2Jp& a, const uint32_t* lds, uint32_t m) {
-  const uint32_t o = 2 * m + (pair_odd() ? 1u : 0u);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(&a);
-#pragma unroll
-  for (int w = 0; w < 36; ++w) dst[w] = lds[w * 128 + o];
-}
+// LDS layout of the G1 reduction: word w of item m's point at w * 64 + m (36 words) -- a wave's
+// stores are conflict-free (the G2 tree's layouts: pair_tree.h).
 __device__ __forceinline__ void g1_lds_put(uint32_t* lds, uint32_t m, const G1J& a) {
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&a);
 #pragma unroll
@@ -354,70 +334,6 @@ __device__ __forceinline__ void shfl_words(J& r, const J& x, uint32_t src) {
   const int addr = (int)((src & 63u) << 2);
 #pragma unroll
   for (int i = 0; i < (int)(sizeof(J) / 4); ++i) rs[i] = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)xs[i]);
-}
-
-// 36 words of one lane at w * 64 + l (the B area of the G2 tree)
-template <class J>
-__device__ __forceinline__ void g1w_put36(uint32_t* lds, uint32_t l, const J& x) {
-  static_assert(sizeof(J) == 144, "36 words");
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(&x);
-#pragma unroll
-  for (int w = 0; w < 36; ++w) lds[w * 64 + l] = src[w];
-}
-template <class J>
-__device__ __forceinline__ void g1w_get36(J& x, const uint32_t* lds, uint32_t l) {
-  static_assert(sizeof(J) == 144, "36 words");
-  uint32_t* dst = reinterpret_cast<uint32_t*>(&x);
-#pragma unroll
-  for (int w = 0; w < 36; ++w) dst[w] = lds[w * 64 + l];
-}
-
-// The tile's G2 tree (rlc_reduce's merges: A = A_l + A_r, B = 2 (B_l + B_r) + A_r) on ONE wave of
-// 32 lane pairs: pair j owns node m = 2 j.  A and B both in LDS (B at w * 64 + lane: the right
-// node's B is the one of pair j + s / 2, i.e. lane + s), so at most two points are live beside the
-// product's fixed registers (B in registers left a 848 B/lane frame).
-__device__ __forceinline__ void rlc_reduce_g2p(uint32_t* lds, uint32_t* ldsB, uint32_t lane, G2J* outA, G2J* outB) {
-  const uint32_t j = lane >> 1, m = 2 * j;
-  {  // level 1: the leaves' B are infinity, so B = A_r
-    G2Jp a, ar;
-    g2p_lds_get(ar, lds, m + 1);
-    g1w_put36(ldsB, lane, ar);
-    g2p_lds_get(a, lds, m);
-    jac_add_lean(a, ar);
-    g2p_lds_put(lds, m, a);
-    wave_lds_sync();
-  }
-#pragma unroll 1
-  for (uint32_t s = 2; s < 64; s <<= 1) {
-    if ((j & (s - 1)) == 0) {  // active pairs read only inactive pairs' entries besides their own
-      G2Jp b, x;
-      g1w_get36(b, ldsB, lane);
-      g1w_get36(x, ldsB, lane + s);
-      jac_add_lean(b, x);
-      jac_dbl(b, b);
-      g2p_lds_get(x, lds, m + s);  // A_r
-      jac_add_lean(b, x);
-      g1w_put36(ldsB, lane, b);
-      g2p_lds_get(b, lds, m);
-      jac_add_lean(b, x);
-      g2p_lds_put(lds, m, b);
-    }
-    wave_lds_sync();
-    if (s == 4 && (j & 3u) == 0) {
-      G2Jp x;
-      g2p_lds_get(x, lds, m);
-      g2p_store_jac(outA + (m >> 3), x);
-      g1w_get36(x, ldsB, lane);
-      g2p_store_jac(outB + (m >> 3), x);
-    }
-  }
-  if (j == 0) {
-    G2Jp x;
-    g2p_lds_get(x, lds, 0);
-    g2p_store_jac(outA + 8, x);
-    g1w_get36(x, ldsB, lane);
-    g2p_store_jac(outB + 8, x);
-  }
 }
 
 // The tile's G1 tree, one lane per item on ONE wave (rlc_reduce1 without workgroup barriers).
@@ -816,6 +732,20 @@ hipError_t launch_sig_items(hipStream_t s, uint32_t n_tiles, const Tile* tiles, 
                      pk_tab, n_pk, key, sus, sums, dec, status);
 #endif
   return hipGetLastError();
+}
+
+// The decode half alone (hbtc_sv.hip's signed-message batches run it ahead of k_sv_items).
+hipError_t launch_sig_decode_only(hipStream_t s, uint32_t n_tiles, const Tile* tiles, const uint32_t* idx,
+                                  const uint8_t* sigs, const int32_t* pk_status, uint32_t n_pk, G2A* dec,
+                                  int32_t* status) {
+  if (n_tiles == 0) return hipSuccess;
+#if HBTC_SIGDEC_PAIR
+  hipLaunchKernelGGL(k_sig_decode_pair, dim3(n_tiles), dim3(64), 0, s, tiles, idx, sigs, pk_status, n_pk, dec,
+                     status);
+  return hipGetLastError();
+#else
+  return launch_sig_decode(s, n_tiles, tiles, idx, sigs, pk_status, n_pk, dec, status);
+#endif
 }
 
 bool sig_exact_built() { return HBTC_SIG_PAIR != 0; }

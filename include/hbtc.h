@@ -34,6 +34,10 @@
  *                            accepted proposer's ciphertext   src/threshold_decryption.rs:94-113
  *   hbtc_sign_shares         SecretKeyShare::sign (hash_g2, sk H): the node's own coin shares
  *                                                                             src/coin.rs:138-147
+ *   hbtc_verify_signed_msgs  PublicKey::verify(&Signature, bytes) of DynamicHoneyBadger's signed votes and
+ *                            key-generation messages, hashed and grouped by signer on the GPU
+ *                                                                             src/dynamic_honey_badger/votes.rs:150-155,
+ *                                                                             dynamic_honey_badger.rs:216,282,425-440
  *   hbtc_g1_msm/hbtc_g2_msm  batched Pippenger MSMs (BivarCommitment::row / Commitment::evaluate,
  *                            src/sync_key_gen.rs:345,366,493); the combines run on the same kernels
  *
@@ -306,6 +310,32 @@ int hbtc_decrypt_shares(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const
  * the scalar and its digits are zeroed as above (they reach the device only as kernel arguments). */
 int hbtc_sign_shares(hbtc_ctx* ctx, uint32_t n, const uint8_t* sk_le32, const uint8_t* msgs,
                      const uint32_t* offsets, uint8_t* out_sig_c96, uint8_t* out_H_c96);
+
+/* PublicKey::verify(&sig_i, msg_i) for n signed messages whose signers are entries of a loaded key
+ * set: DynamicHoneyBadger's signed votes (VoteCounter::validate,
+ * src/dynamic_honey_badger/votes.rs:150-155) and signed key-generation messages
+ * (DynamicHoneyBadger::verify_signature, dynamic_honey_badger.rs:425-440, called at :216 and for every
+ * message of every contribution of a batch at :282).  The key set holds the validators' individual
+ * public keys in node order (hbtc_keyset_load); the caller appends a joining candidate's key as one
+ * more entry (candidate_key, :433-438).  signer[i] indexes the key set; msg_i =
+ * msgs[offsets[i] .. offsets[i+1]) under the offset rule of the hash batches; items in any order.
+ *   status[i] is what hbtc_verify_sigs(pk[signer[i]], hbtc_hash_g2(msg_i), sig_i) gives: HBTC_ACCEPT;
+ *   HBTC_REJECT; HBTC_DECODE_ERR for a signature serde would refuse or that is off the subgroup, and
+ *   for every item of a key whose key-set status is not ACCEPT; HBTC_UNKNOWN_SENDER where signer[i]
+ *   is not below the key-set size (the reference's pk_opt == None: false).
+ * Routes, with equal decisions: HBTC_MODE_PER_SHARE and calls below hbtc_set_exact_below check every
+ * item exactly.  Other calls hash on the GPU and take the pair batch of hbtc_verify_sigs with the
+ * signers' keys gathered from the key set.  hbtc_set_exact_below(ctx, 0) ("always batch") selects the
+ * grouped path: the items are signed by few keys, so they are sorted by signer and, per signer j,
+ * e(P_j, sum r_i H_i) == e(G1, sum r_i sig_i) is checked with one random scalar per item -- two
+ * 128-bit G2 multiplications per item and one Miller loop per signer, instead of a key decode, a G1
+ * multiplication, a line table and a Miller loop per item; the items of a signer whose check fails
+ * get exact individual verdicts.  It is not the default because it measured slower than the pair
+ * batch at 1,000 signers and 64 k items.  n == 0: HBTC_OK.  HBTC_ERR_ARG for a NULL
+ * signer, offsets, sig_c96 or status, NULL msgs with offsets[n] != 0, or bad offsets. */
+int hbtc_verify_signed_msgs(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n, const uint32_t* signer,
+                            const uint8_t* msgs, const uint32_t* offsets, const uint8_t* sig_c96,
+                            int32_t* status);
 
 /* ---- host hashes (no context, no GPU) ----------------------------------------------------- */
 /* threshold_crypto's crate-internal hash_g2(msg) -> compressed G2 (96 B), and hash_g1_g2(g1, msg)
@@ -691,7 +721,8 @@ int hbtc_merkle_validate_dev(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const 
  * (hbtc_decrypt_shares) and "own_sig" (hbtc_sign_shares), each the whole call on the device, their
  * stages counting under "hash", the pair check's families ("pb_items", "pb_lines", "pb_ml",
  * "pb_checks" of the pair batch; "pb_decode", "sig_items", "chk_leaves" of the exact checks) and
- * "mul".  Reading
+ * "mul"; "sv_items" (signature decode and the item pass), "sv_sums" (the signers' trees) and
+ * "sv_checks" (the signer-level pair checks) of hbtc_verify_signed_msgs.  Reading
  * synchronises the stream. */
 int hbtc_timing_enable(hbtc_ctx* ctx, int enable);
 int hbtc_timing_read(hbtc_ctx* ctx, const char* family, double* total_ms, uint64_t* launches);

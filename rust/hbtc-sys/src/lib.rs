@@ -333,6 +333,27 @@ impl Context {
         Ok((sig, h))
     }
 
+    /// PublicKey::verify of DynamicHoneyBadger's signed votes and key-generation messages
+    /// (src/dynamic_honey_badger/votes.rs:150-155, dynamic_honey_badger.rs:425-440), grouped by signer:
+    /// `signer[i]` indexes the key set (the validators' public keys, a candidate's appended), message i
+    /// is msgs[offsets[i] .. offsets[i + 1]), `sig_c96` holds one 96-byte signature per message.
+    /// Returns one HBTC_* status per message.
+    pub fn verify_signed_msgs(&self, keyset_id: u32, signer: &[u32], msgs: &[u8], offsets: &[u32],
+                              sig_c96: &[u8]) -> Result<Vec<i32>> {
+        assert!(!offsets.is_empty() && offsets[0] == 0, "offsets[0] must be 0");
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]), "offsets must be non-decreasing");
+        let n = offsets.len() - 1;
+        assert!(offsets[n] as usize <= msgs.len(), "offsets past the message bytes");
+        assert_eq!(signer.len(), n, "one signer per message");
+        assert_eq!(sig_c96.len(), 96 * n, "one 96-byte signature per message");
+        let mut status = vec![0i32; n];
+        self.ok(unsafe {
+            ffi::hbtc_verify_signed_msgs(self.raw, keyset_id, n as u32, signer.as_ptr(), msgs.as_ptr(),
+                                         offsets.as_ptr(), sig_c96.as_ptr(), status.as_mut_ptr())
+        })?;
+        Ok(status)
+    }
+
     /// out[p * n_x + j] = poly_p(x_j) over Fr (32-byte LE each): n_poly rows of n_coeff coefficients.
     pub fn fr_poly_eval(&self, n_coeff: u32, coeffs_le32: &[u8], x_le32: &[u8]) -> Result<Vec<u8>> {
         assert_eq!(x_le32.len() % 32, 0);
