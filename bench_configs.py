@@ -67,6 +67,16 @@ checked against the construction after timing:
       ratio and the HIP-event spans ("sv_items", "sv_sums", "sv_checks", "hash" and the exact
       route's families).
 
+  coin One Threshold Coin ROUND of 64 instances at N = 1000 (t = 334) and at C4's N = 10^4 (t = 3334)
+      (not in the default list), host buffers, a key set with its master key, coin_inputs' shares
+      (1% wrong): (a) one hbtc_coin_decide call; (b) hbtc_coin_epoch_submit, four tickets in
+      flight; (c) the composed hbtc_verify_sig_shares + first t ACCEPTed (host) + hbtc_combine_sigs
+      + hbtc_verify_sigs against the master key -- in the same process, interleaved in every
+      repeat after a warm-up.  Statuses, signatures and coin statuses are checked against the
+      construction ((master h_k) G2) before any time is reported.  Reports ms per round for each,
+      the ratios of (a) and (b) to (c), and the HIP-event spans ("coin_gather", "coin_final" and
+      the combines' families).
+
   bc  Reliable Broadcast of one HoneyBadger epoch at N = 256 (the largest network hbbft's
       reed-solomon-erasure coding accepts: k + p <= 256), one node's view: the N^2 = 65,536 Echo
       proofs it receives validated (Proof::validate, src/broadcast/merkle.rs:82-102, via
@@ -76,7 +86,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own,sv] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own,sv,coin] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -1214,6 +1224,114 @@ def bench_signed_msgs(ctx, steps, warmup, n_signers=1000, n_items=1 << 16):
     return res
 
 
+def bench_coin_round(ctx, steps, warmup, shapes=((1000, 64), (10000, 64))):
+    """coin: hbtc_coin_decide and hbtc_coin_epoch_submit against the composed calls (see the docstring)."""
+    steps = max(steps, 3)
+    families = ("sig_items", "chk_tiles", "chk_subs", "chk_leaves", "rlc_finalize", "lagrange", "comb_decode",
+                "comb_digits", "combine", "coin_gather", "coin_final", "pb_items", "pb_ml", "pb_checks")
+
+    def stat(xs):
+        return {"median_ms": round(float(np.median(xs)), 3), "min_ms": round(min(xs), 3),
+                "max_ms": round(max(xs), 3)}
+
+    def spans(fn):
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        fn()
+        ctx.sync()
+        out = {}
+        for fam in families:
+            ms, launches = ctx.timing_read(fam)
+            if launches:
+                out[fam] = {"ms": round(ms, 3), "launches": int(launches)}
+        ctx.timing_enable(False)
+        return out
+
+    out = {}
+    for n, n_inst in shapes:
+        t0 = time.time()
+        inp = coin_inputs(ctx, n, n_inst)
+        t, off, idx = inp["t"], inp["offsets"], inp["idx"]
+        H, sigs = inp["H"], inp["sigs"]
+        ks, bad = ctx.keyset_load(inp["pk"])
+        assert bad == 0
+        mpk, _ = ctx.g1_mul(G1_GEN, fr_bytes([inp["master"]]))
+        mpk = mpk.tobytes()
+        ctx.keyset_set_master(ks, mpk)
+        want_sig, _ = ctx.g2_mul(G2_GEN, fr_bytes([inp["master"] * h % R for h in inp["hs"]]))
+        want_sig = want_sig.reshape(n_inst, 96)
+        sig2 = sigs.reshape(-1, 96)
+        log("coin: setup %.1fs (N = %d, t = %d, %d instances, %d shares)" % (time.time() - t0, n, t, n_inst, n * n_inst))
+        last = {}
+
+        def one_call():
+            last["a"] = ctx.coin_decide(ks, H, None, idx, sigs, t, offsets=off)
+
+        def ticketed():  # four rounds in flight, collected in order: per-round time = the batch / 4
+            pend = [ctx.coin_epoch_submit(ks, H, off, idx, sigs, t) for _ in range(4)]
+            last["b"] = [p.wait() for p in pend][-1]
+
+        def composed():
+            st = ctx.verify_sig_shares(ks, H, None, idx, sigs, offsets=off)
+            pos = [np.flatnonzero(st[off[k]:off[k + 1]] == N.ACCEPT)[:t] + int(off[k]) for k in range(n_inst)]
+            sel = np.concatenate(pos)
+            o, par, cst = ctx.combine_sigs([len(p) for p in pos], idx[sel], np.ascontiguousarray(sig2[sel]), t)
+            coin = np.array(cst, np.int32)
+            ok = [k for k in range(n_inst) if coin[k] == N.ACCEPT]
+            if ok:
+                coin[ok] = ctx.verify_sigs([mpk] * len(ok), [H[96 * k:96 * k + 96].tobytes() for k in ok],
+                                           [o[k] for k in ok])
+            last["c"] = (st, o, par, coin)
+
+        for _ in range(max(warmup, 1)):
+            one_call()
+            ticketed()
+            composed()
+        # the construction first: statuses as generated, every coin ACCEPT with signature (master h_k) G2
+        a, b, c = last["a"], last["b"], last["c"]
+        for name, r in (("coin_decide", a), ("coin_epoch_submit", b), ("composed", c)):
+            if not np.array_equal(np.asarray(r[0])[:n * n_inst], inp["expected"]):
+                raise SystemExit("coin: %s item statuses differ from the construction at N = %d" % (name, n))
+            if [int(x) for x in np.asarray(r[3])[:n_inst]] != [N.ACCEPT] * n_inst:
+                raise SystemExit("coin: %s coin statuses are not all ACCEPT at N = %d" % (name, n))
+            for k in range(n_inst):
+                if bytes(r[1][k]) != want_sig[k].tobytes():
+                    raise SystemExit("coin: %s signature %d is not (master h_k) G2 at N = %d" % (name, k, n))
+            if list(np.asarray(r[2])[:n_inst]) != list(np.asarray(a[2])[:n_inst]):
+                raise SystemExit("coin: %s parities differ at N = %d" % (name, n))
+        times = {"coin_decide": [], "coin_epoch_submit": [], "composed": []}
+        for _ in range(steps):  # interleaved: every repeat runs the three back to back
+            for name, fn, div in (("coin_decide", one_call, 1), ("coin_epoch_submit", ticketed, 4),
+                                  ("composed", composed, 1)):
+                t1 = time.perf_counter()
+                fn()
+                times[name].append((time.perf_counter() - t1) * 1e3 / div)
+        r = {name: stat(ts) for name, ts in times.items()}
+        r["coin_decide_over_composed"] = round(r["coin_decide"]["median_ms"] / r["composed"]["median_ms"], 3)
+        r["coin_epoch_submit_over_composed"] = round(r["coin_epoch_submit"]["median_ms"] / r["composed"]["median_ms"], 3)
+        r["spans_coin_decide"] = spans(one_call)
+        r["spans_coin_epoch_submit_x4"] = spans(ticketed)
+        r["spans_composed"] = spans(composed)
+        r["t"] = t
+        r["results_match_construction"] = True
+        out["N%d_x%d" % (n, n_inst)] = r
+        ctx.keyset_free(ks)
+    first = out["N%d_x%d" % shapes[0]]
+    res = {
+        "metric": "ms per Threshold Coin round (hbtc_coin_decide, N = %d, %d instances)" % shapes[0],
+        "value": first["coin_decide"]["median_ms"], "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": warmup,
+        "higher_is_better": False, "dtype": "u32 (381-bit Montgomery limbs)",
+        "data": "synthetic (coin_inputs: 1% wrong shares); host buffers (PCIe-inclusive), Python marshalling "
+                "included; coin_epoch_submit timed four in flight, divided by four",
+        "config": {"workload": "coin: one round by hbtc_coin_decide / hbtc_coin_epoch_submit against "
+                               "hbtc_verify_sig_shares + hbtc_combine_sigs + hbtc_verify_sigs on the same inputs",
+                   "shapes": [list(s) for s in shapes],
+                   "mode": "rlc" if ctx_mode[0] == N.MODE_RLC else "per_share"},
+    }
+    res.update(out)
+    return res
+
+
 def bench_broadcast(ctx, n, value_bytes, steps, warmup):
     """bc: one node's Reliable Broadcast work for an epoch of n proposers (see the docstring)."""
     from hbbft_amd import broadcast as G
@@ -1394,6 +1512,8 @@ def main():
                 out = bench_own_shares(ctx, args.td_bytes, steps, warmup)
             elif c == "sv":
                 out = bench_signed_msgs(ctx, steps, warmup)
+            elif c == "coin":
+                out = bench_coin_round(ctx, steps, warmup)
             elif c == "kg":
                 out = bench_keygen(ctx, args.nodes, steps, warmup, parent=args.kg_parent)
             elif c == "c5p":

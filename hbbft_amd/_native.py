@@ -147,6 +147,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_uint64)]),
     "hbtc_sig_epoch_submit": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P,
                                      ctypes.POINTER(ctypes.c_uint64)]),
+    "hbtc_coin_epoch_submit": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P,
+                                      ctypes.POINTER(ctypes.c_uint64)]),
     "hbtc_wait": (_I32, [_P, ctypes.c_uint64]),
     "hbtc_node_verify_sig_shares_dev": (_I32, [_P, _U32, _P]),
     "hbtc_node_verify_dec_shares_dev": (_I32, [_P, _U32, _P]),
@@ -424,7 +426,9 @@ class Context:
     # ---- verification
     def coin_decide(self, keyset, H, counts, idx, sigs, t, offsets=None):
         """One Threshold Coin round (hbtc.h hbtc_coin_decide): item statuses, combined signatures,
-        parity bits and coin statuses (ACCEPT = the combined signature passed the master check)."""
+        parity bits and coin statuses (ACCEPT = the combined signature passed the master check).
+        Any t >= 1: above 64 the combine and the master check are the Pippenger combines over one
+        selection (no speculation)."""
         off = _offsets(offsets if offsets is not None else counts, offsets is not None)
         n_inst = off.size - 1
         Hb, sb = _join(H, 96), _join(sigs, 96)
@@ -545,6 +549,23 @@ class Context:
         self._check(self.lib.hbtc_sig_epoch_submit(self.h, keyset, n_inst, _ptr(Hb), _ptr(off), _ptr(ix), _ptr(sb),
                                                    t, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
                                                    _ptr(outs[3]), ctypes.byref(tk)), "hbtc_sig_epoch_submit")
+        return self._hold(tk.value, outs, (off,))
+
+    def coin_epoch_submit(self, keyset, H, offsets, idx, sigs, t, outs=None):
+        """The coin round without blocking (hbtc.h hbtc_coin_epoch_submit; any t >= 1, the key set
+        needs its master key): wait() gives (status, sig [n_inst, 96], parity, coin status), the
+        results of coin_decide with the coin status merged on the device."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_inst, n = off.size - 1, int(off[-1])
+        Hb, sb = _join(H, 96), _join(sigs, 96)
+        ix = np.ascontiguousarray(idx, dtype=np.uint32)
+        if outs is None:
+            outs = (np.empty(max(n, 1), np.int32), np.empty((max(n_inst, 1), 96), np.uint8),
+                    np.empty(max(n_inst, 1), np.uint8), np.empty(max(n_inst, 1), np.int32))
+        tk = ctypes.c_uint64()
+        self._check(self.lib.hbtc_coin_epoch_submit(self.h, keyset, n_inst, _ptr(Hb), _ptr(off), _ptr(ix), _ptr(sb),
+                                                    t, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                                    _ptr(outs[3]), ctypes.byref(tk)), "hbtc_coin_epoch_submit")
         return self._hold(tk.value, outs, (off,))
 
     def verify_sigs(self, pks, H, sigs):

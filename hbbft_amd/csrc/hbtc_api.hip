@@ -54,6 +54,7 @@ struct Keyset {
   uint32_t calls = 0;            // RLC verification calls on this key set
   uint32_t n = 0;
   G1A* master = nullptr;         // hbtc_keyset_set_master: the decoded master public key
+  uint8_t* master_c48 = nullptr; // ... and its canonical compressed bytes (the large-t coin rounds compare against them)
   uint8_t* c48 = nullptr;        // the keys compressed, built at the first hbtc_verify_signed_msgs that needs them
 };
 
@@ -1251,6 +1252,109 @@ int msm_run(hbtc_ctx* c, hipStream_t st, const MsmPlan& p, const uint32_t* d_sca
   });
 }
 
+// The selection of a combine and its coefficients: the first t items of every instance (with
+// d_item_status: the first t ACCEPTed ones), their Lagrange coefficients at 0 and the duplicate
+// flags, enqueued on `sc`.  The arrays live in the lane's comb.* workspace, which msm_run never
+// touches, so several MSMs ordered on `sc` may read one selection (the coin round's G2 combine
+// and its G1 master check).
+struct CombSel {
+  uint32_t *sel_pos, *sel_idx, *sel_cnt, *dup, *bad;
+  Fr* lambda;
+};
+int combine_select(hbtc_ctx* c, hipStream_t sc, uint32_t n_inst, const uint32_t* d_off, uint32_t t,
+                   const int32_t* d_item_status, const uint32_t* d_idx, CombSel* sel) {
+  const uint64_t terms = (uint64_t)n_inst * t;
+  uint32_t *d_sel_pos, *d_sel_idx, *d_sel_cnt, *d_dup, *d_bad;
+  Fr *d_lambda, *d_lws;
+  HB_TRY(wst(c, "comb.lws", terms, &d_lws));
+  HB_TRY(wst(c, "comb.sel_pos", terms, &d_sel_pos));
+  HB_TRY(wst(c, "comb.sel_idx", terms, &d_sel_idx));
+  HB_TRY(wst(c, "comb.sel_cnt", n_inst, &d_sel_cnt));
+  HB_TRY(wst(c, "comb.dup", n_inst, &d_dup));
+  HB_TRY(wst(c, "comb.bad", n_inst, &d_bad));
+  HB_TRY(wst(c, "comb.lambda", terms, &d_lambda));
+  HB_CHECK(c, launch_zero_u32(sc, d_dup, n_inst));
+  HB_CHECK(c, launch_zero_u32(sc, d_bad, n_inst));
+  LagrangeFact lf{};
+  if (c->lagrange_fact && !c->fact) {
+    // once per context: 0! .. FACT_N! and their inverses, then every stream may read them.  One
+    // allocation holds both tables and the build's partial products (nothing is freed in the
+    // middle of the pipeline: hipFree synchronises the device), and the tables are published
+    // only once built; if any step fails the context keeps the O(t) coefficients instead
+    // (ADVICE r05: a half-built table would give wrong coefficients under an ACCEPT status).
+    const size_t n = FACT_N + 1;
+    Fr* tab = nullptr;
+    hipError_t e = hipMalloc(&tab, sizeof(Fr) * (2 * n + FACT_N / 256 + 1));
+    if (e == hipSuccess) e = launch_fact_tables(sc, FACT_N, tab + 2 * n, tab, tab + n);
+    if (e == hipSuccess) e = hipStreamSynchronize(sc);
+    if (e == hipSuccess) {
+      c->fact = tab;
+      c->inv_fact = tab + n;
+    } else {
+      if (tab) (void)hipFree(tab);
+      c->lagrange_fact = false;
+      HB_CHECK(c, e);
+    }
+  }
+  if (c->lagrange_fact) {
+    uint32_t* d_done;
+    HB_TRY(wst(c, "comb.fact_done", n_inst, &d_done));
+    lf = LagrangeFact{c->fact, c->inv_fact, FACT_N, d_sel_cnt, d_done};
+  }
+  HB_TRY(timed_on(c, sc, "lagrange", [&] {
+    hipError_t e = launch_select(sc, n_inst, d_off, t, d_item_status, d_idx, d_sel_pos, d_sel_idx,
+                                 d_sel_cnt);
+    if (e != hipSuccess) return e;
+    return launch_lagrange_sel(sc, n_inst, t, d_sel_idx, d_lambda, d_lws, d_dup,
+                               c->lagrange_fact ? &lf : nullptr);
+  }));
+  *sel = CombSel{d_sel_pos, d_sel_idx, d_sel_cnt, d_dup, d_bad, d_lambda};
+  return HBTC_OK;
+}
+
+// The G2 combine of a selection on `sc`: the selected shares gathered from the decoded array of
+// the verification that produced d_item_status when it ran over these very arrays (else decoded
+// here), GLS digits and the Pippenger reduction.  *dec_used: that decoded array, or null.
+int combine_g2_sel(hbtc_ctx* c, hipStream_t sc, const CombSel& sel, uint32_t n_inst, uint32_t n_items,
+                   uint32_t t, const uint8_t* d_pts, const int32_t* d_item_status, uint8_t* d_out,
+                   uint8_t* d_parity, int32_t* d_inst_status, const G2A** dec_used) {
+  const uint64_t terms = (uint64_t)n_inst * t;
+  uint32_t *d_sel_pos = sel.sel_pos, *d_sel_cnt = sel.sel_cnt, *d_dup = sel.dup, *d_bad = sel.bad;
+  Fr* d_lambda = sel.lambda;
+  const MsmPlan plan = msm_plan(n_inst, t);
+  const auto& ld = c->last_dec;
+  const G2A* dec2 = (d_item_status && ld.status == d_item_status && ld.shares == d_pts &&
+                     ld.n_items == n_items)
+                        ? ld.dec2
+                        : nullptr;
+  G2A* d_aff;
+  HB_TRY(wst(c, "comb.g2", terms, &d_aff));
+  HB_TRY(timed_on(c, sc, "comb_decode", [&] {
+    if (dec2) return launch_msm_gather_g2(sc, n_inst, t, d_sel_pos, d_sel_cnt, dec2, d_aff);
+    return launch_msm_decode_g2(sc, n_inst, t, t, d_pts, d_sel_pos, d_sel_cnt, d_item_status,
+                                nullptr, d_aff, d_bad);
+  }));
+  if (c->g2_gls) {
+    // ψ = [x] on G2: four 64-bit terms per share (k_msm_gls_g2), so the Horner chain of the
+    // final pass is ~64 doublings instead of ~255 (the G2 combine is the lane's latency tail)
+    G2A* d_aff4;
+    uint32_t* d_sc4;
+    HB_TRY(wst(c, "comb.g2x4", 4 * terms, &d_aff4));
+    HB_TRY(wst(c, "comb.lws4", 4 * terms * 8, &d_sc4));
+    HB_TRY(timed_on(c, sc, "comb_digits", [&] {
+      return launch_msm_gls_g2(sc, n_inst, t, (const uint32_t*)d_lambda, d_aff, d_sc4, d_aff4);
+    }));
+    const MsmPlan plan4 = msm_plan(n_inst, 4 * t, 64);
+    HB_TRY(msm_run<Fq2>(c, sc, plan4, d_sc4, d_aff4, d_sel_cnt, t, d_bad, d_dup, d_inst_status,
+                        d_out, d_parity));
+  } else {
+    HB_TRY(msm_run<Fq2>(c, sc, plan, (const uint32_t*)d_lambda, d_aff, d_sel_cnt, t, d_bad, d_dup,
+                        d_inst_status, d_out, d_parity));
+  }
+  *dec_used = dec2;
+  return HBTC_OK;
+}
+
 // Lagrange combine on s_comb: ordered after everything already on the main stream (its inputs),
 // overlapped with whatever the main stream does next.  The first t items of every instance are
 // combined; with d_item_status, the first t items whose status is ACCEPT (hbbft combines only
@@ -1305,50 +1409,10 @@ int combine_run(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets
                                {dec, dec ? n_items * (group == 1 ? sizeof(G1A) : sizeof(G2A)) : 0}});
   }
   const uint64_t terms = (uint64_t)n_inst * t;
-  uint32_t *d_sel_pos, *d_sel_idx, *d_sel_cnt, *d_dup, *d_bad;
-  Fr *d_lambda, *d_lws;
-  HB_TRY(wst(c, "comb.lws", terms, &d_lws));
-  HB_TRY(wst(c, "comb.sel_pos", terms, &d_sel_pos));
-  HB_TRY(wst(c, "comb.sel_idx", terms, &d_sel_idx));
-  HB_TRY(wst(c, "comb.sel_cnt", n_inst, &d_sel_cnt));
-  HB_TRY(wst(c, "comb.dup", n_inst, &d_dup));
-  HB_TRY(wst(c, "comb.bad", n_inst, &d_bad));
-  HB_TRY(wst(c, "comb.lambda", terms, &d_lambda));
-  HB_CHECK(c, launch_zero_u32(sc, d_dup, n_inst));
-  HB_CHECK(c, launch_zero_u32(sc, d_bad, n_inst));
-  LagrangeFact lf{};
-  if (c->lagrange_fact && !c->fact) {
-    // once per context: 0! .. FACT_N! and their inverses, then every stream may read them.  One
-    // allocation holds both tables and the build's partial products (nothing is freed in the
-    // middle of the pipeline: hipFree synchronises the device), and the tables are published
-    // only once built; if any step fails the context keeps the O(t) coefficients instead
-    // (ADVICE r05: a half-built table would give wrong coefficients under an ACCEPT status).
-    const size_t n = FACT_N + 1;
-    Fr* tab = nullptr;
-    hipError_t e = hipMalloc(&tab, sizeof(Fr) * (2 * n + FACT_N / 256 + 1));
-    if (e == hipSuccess) e = launch_fact_tables(sc, FACT_N, tab + 2 * n, tab, tab + n);
-    if (e == hipSuccess) e = hipStreamSynchronize(sc);
-    if (e == hipSuccess) {
-      c->fact = tab;
-      c->inv_fact = tab + n;
-    } else {
-      if (tab) (void)hipFree(tab);
-      c->lagrange_fact = false;
-      HB_CHECK(c, e);
-    }
-  }
-  if (c->lagrange_fact) {
-    uint32_t* d_done;
-    HB_TRY(wst(c, "comb.fact_done", n_inst, &d_done));
-    lf = LagrangeFact{c->fact, c->inv_fact, FACT_N, d_sel_cnt, d_done};
-  }
-  HB_TRY(timed_on(c, sc, "lagrange", [&] {
-    hipError_t e = launch_select(sc, n_inst, d_off, t, d_item_status, d_idx, d_sel_pos, d_sel_idx,
-                                 d_sel_cnt);
-    if (e != hipSuccess) return e;
-    return launch_lagrange_sel(sc, n_inst, t, d_sel_idx, d_lambda, d_lws, d_dup,
-                               c->lagrange_fact ? &lf : nullptr);
-  }));
+  CombSel sel;
+  HB_TRY(combine_select(c, sc, n_inst, d_off, t, d_item_status, d_idx, &sel));
+  uint32_t *d_sel_pos = sel.sel_pos, *d_sel_cnt = sel.sel_cnt, *d_dup = sel.dup, *d_bad = sel.bad;
+  Fr* d_lambda = sel.lambda;
   const MsmPlan plan = msm_plan(n_inst, t);
   const size_t pb = group == 1 ? 48 : 96;
   if (group == 1) {
@@ -1388,35 +1452,9 @@ int combine_run(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets
                                {d_item_status, d_item_status ? (size_t)n_items * 4 : 0},
                                {dec, dec ? n_items * sizeof(G1A) : 0}});
   }
-  const auto& ld = c->last_dec;
-  const G2A* dec2 = (d_item_status && ld.status == d_item_status && ld.shares == d_pts &&
-                     ld.n_items == n_items)
-                        ? ld.dec2
-                        : nullptr;
-  G2A* d_aff;
-  HB_TRY(wst(c, "comb.g2", terms, &d_aff));
-  HB_TRY(timed_on(c, sc, "comb_decode", [&] {
-    if (dec2) return launch_msm_gather_g2(sc, n_inst, t, d_sel_pos, d_sel_cnt, dec2, d_aff);
-    return launch_msm_decode_g2(sc, n_inst, t, t, d_pts, d_sel_pos, d_sel_cnt, d_item_status,
-                                nullptr, d_aff, d_bad);
-  }));
-  if (c->g2_gls) {
-    // ψ = [x] on G2: four 64-bit terms per share (k_msm_gls_g2), so the Horner chain of the
-    // final pass is ~64 doublings instead of ~255 (the G2 combine is the lane's latency tail)
-    G2A* d_aff4;
-    uint32_t* d_sc4;
-    HB_TRY(wst(c, "comb.g2x4", 4 * terms, &d_aff4));
-    HB_TRY(wst(c, "comb.lws4", 4 * terms * 8, &d_sc4));
-    HB_TRY(timed_on(c, sc, "comb_digits", [&] {
-      return launch_msm_gls_g2(sc, n_inst, t, (const uint32_t*)d_lambda, d_aff, d_sc4, d_aff4);
-    }));
-    const MsmPlan plan4 = msm_plan(n_inst, 4 * t, 64);
-    HB_TRY(msm_run<Fq2>(c, sc, plan4, d_sc4, d_aff4, d_sel_cnt, t, d_bad, d_dup, d_inst_status,
-                        d_out, d_parity));
-  } else {
-    HB_TRY(msm_run<Fq2>(c, sc, plan, (const uint32_t*)d_lambda, d_aff, d_sel_cnt, t, d_bad, d_dup,
-                        d_inst_status, d_out, d_parity));
-  }
+  const G2A* dec2;
+  HB_TRY(combine_g2_sel(c, sc, sel, n_inst, n_items, t, d_pts, d_item_status, d_out, d_parity,
+                        d_inst_status, &dec2));
   return note_comb_reads(c, {{d_idx, (size_t)n_items * 4}, {d_pts, n_items * pb},
                              {d_item_status, d_item_status ? (size_t)n_items * 4 : 0},
                              {dec2, dec2 ? n_items * sizeof(G2A) : 0}});
@@ -1449,6 +1487,101 @@ int combine_dev(hbtc_ctx* c, int group, uint32_t n_inst, const uint32_t* offsets
     v.push_back({lo, lo + r.second, ev, c->lane});
   }
   return HBTC_OK;
+}
+
+// The status-driven tail of a coin round on the lane's combine stream, behind the share checks
+// that wrote d_item: the G2 combine of the first t ACCEPTed shares of every instance (d_sig_out,
+// d_par), the master check sum l_i pk_i == master pk over the key set's resident shares, and the
+// coin status merged on the device (d_coin: the combine's failure, else ACCEPT / REJECT).
+//   t <= COMB_SMALL_T: the one-workgroup pair, group 2 then group 1 with cmp (no speculation).
+//   above: ONE selection and ONE set of coefficients (combine_select) serve both combines -- the
+//   G2 Pippenger over the shares (combine_g2_sel) and then, on the same stream, the G1 Pippenger
+//   over pk[sel_idx] gathered by node index; both MSMs recycle the msm.* workspace in stream order,
+//   while the selection and lambda live in comb.*, which neither writes.  The sum is compared with
+//   the master key as canonical compressed bytes (Keyset::master_c48, k_coin_final).
+int coin_combine_dev(hbtc_ctx* c, const Keyset* ks, uint32_t n_inst, const uint32_t* offsets,
+                     uint32_t n_items, const uint32_t* d_idx, const uint8_t* d_sig, uint32_t t,
+                     const int32_t* d_item, uint8_t* d_sig_out, uint8_t* d_par, int32_t* d_coin) {
+  if (n_inst == 0) return HBTC_OK;
+  if (!aligned16(d_sig) || !aligned16(d_sig_out))
+    return fail(c, HBTC_ERR_ARG, "point arrays must be 16-byte aligned");
+  hipStream_t sc = c->s_comb;
+  void* p;
+  HB_TRY(stage_upload(c, "comb.offsets", offsets, ((size_t)n_inst + 1) * 4, sc, &p));
+  const uint32_t* d_off = static_cast<const uint32_t*>(p);
+  int32_t *d_cst, *d_mst;
+  HB_TRY(wst(c, "coin.cst", n_inst, &d_cst));
+  HB_TRY(wst(c, "coin.master", n_inst, &d_mst));
+  const auto& ld = c->last_dec;
+  if (c->comb_small && t <= COMB_SMALL_T) {
+    const bool same = ld.status == d_item && ld.shares == d_sig && ld.n_items == n_items;
+    const void* dec = same ? (const void*)ld.dec2 : nullptr;
+    CombSmallArgs a{};
+    a.t = t;
+    a.offsets = d_off;
+    a.item_status = d_item;
+    a.idx = d_idx;
+    a.pts = d_sig;
+    a.dec = dec;
+    a.inst_status = d_cst;
+    a.out = d_sig_out;
+    a.parity = d_par;
+    CombSmallArgs m{};
+    m.t = t;
+    m.offsets = d_off;
+    m.item_status = d_item;
+    m.idx = d_idx;
+    m.dec = ks->pk;
+    m.by_node = 1;
+    m.n_nodes = ks->n;
+    m.inst_status = d_mst;
+    m.cmp = ks->master;
+    m.xtab = ks->tab;
+    HB_TRY(timed_on(c, sc, "combine", [&] {
+      hipError_t e = launch_comb_small(sc, 2, n_inst, 1, a);
+      if (e != hipSuccess) return e;
+      return launch_comb_small(sc, 1, n_inst, 1, m);
+    }));
+    HB_TRY(timed_on(c, sc, "coin_final", [&] {
+      return launch_coin_final(sc, n_inst, d_cst, d_mst, nullptr, nullptr, d_coin);
+    }));
+    return note_comb_reads(c, {{d_idx, (size_t)n_items * 4}, {d_sig, (size_t)n_items * 96},
+                               {d_item, (size_t)n_items * 4}, {dec, dec ? n_items * sizeof(G2A) : 0}});
+  }
+  if (!ks->master_c48) return fail(c, HBTC_ERR_ARG, "key set has no compressed master key");
+  const uint64_t terms = (uint64_t)n_inst * t;
+  CombSel sel;
+  HB_TRY(combine_select(c, sc, n_inst, d_off, t, d_item, d_idx, &sel));
+  const G2A* dec2;
+  HB_TRY(combine_g2_sel(c, sc, sel, n_inst, n_items, t, d_sig, d_item, d_sig_out, d_par, d_cst, &dec2));
+  // the master check: sum l_i pk_i over the same selection and the same coefficients
+  G1A* d_pk;
+  uint8_t* d_sum;
+  HB_TRY(wst(c, "coin.pk", terms, &d_pk));
+  HB_TRY(wst(c, "coin.sum", (size_t)48 * n_inst, &d_sum));
+  HB_TRY(timed_on(c, sc, "coin_gather", [&] {
+    return launch_coin_gather_pk(sc, n_inst, t, sel.sel_idx, sel.sel_cnt, ks->pk, ks->n, d_pk);
+  }));
+  if (c->g1_glv) {
+    G1A* d_pk2;
+    uint32_t* d_sc2;
+    HB_TRY(wst(c, "coin.pkx2", 2 * terms, &d_pk2));
+    HB_TRY(wst(c, "coin.lws2", 2 * terms * 8, &d_sc2));
+    HB_TRY(timed_on(c, sc, "comb_digits", [&] {
+      return launch_msm_glv_g1(sc, n_inst, t, (const uint32_t*)sel.lambda, d_pk, d_sc2, d_pk2);
+    }));
+    const MsmPlan plan2 = msm_plan(n_inst, 2 * t, 128);
+    HB_TRY(msm_run<Fq>(c, sc, plan2, d_sc2, d_pk2, sel.sel_cnt, t, sel.bad, sel.dup, d_mst, d_sum, nullptr));
+  } else {
+    const MsmPlan plan = msm_plan(n_inst, t);
+    HB_TRY(msm_run<Fq>(c, sc, plan, (const uint32_t*)sel.lambda, d_pk, sel.sel_cnt, t, sel.bad, sel.dup,
+                       d_mst, d_sum, nullptr));
+  }
+  HB_TRY(timed_on(c, sc, "coin_final", [&] {
+    return launch_coin_final(sc, n_inst, d_cst, nullptr, d_sum, ks->master_c48, d_coin);
+  }));
+  return note_comb_reads(c, {{d_idx, (size_t)n_items * 4}, {d_sig, (size_t)n_items * 96},
+                             {d_item, (size_t)n_items * 4}, {dec2, dec2 ? n_items * sizeof(G2A) : 0}});
 }
 
 // First pad block of every item (16 pad bytes per ChaCha block; blk[n] = the call's block count).
@@ -1554,13 +1687,21 @@ int finish_ticket(hbtc_ctx* c, hbtc_ctx::Ticket& T) {
 // D2H of the results, all on that lane's stream (group 1: DecryptionShares, 2: SignatureShares).
 // With v_off (group 1, t > 0): the ciphertexts' v ride in the same staging, the seed and the pad
 // follow the combine on the lane's stream and the plaintexts come back with the other results.
+// With coin (group 2, t > 0, a key set with its master key): the combine is the coin round's
+// (coin_combine_dev), and the ticket's inst_status slot carries the coin status merged on the device.
 int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H,
                  const uint8_t* w, const uint32_t* offsets, const uint32_t* idx, const uint8_t* items,
                  uint32_t t, int32_t* status, uint8_t* out, uint8_t* parity, int32_t* inst_status,
                  uint64_t* ticket, const uint8_t* v = nullptr, const uint32_t* v_off = nullptr,
-                 uint8_t* out_plain = nullptr) {
+                 uint8_t* out_plain = nullptr, bool coin = false) {
   uint32_t n;
   HB_TRY(check_offsets(c, n_inst, offsets, &n));
+  Keyset* coin_ks = nullptr;
+  if (coin) {  // refused before anything is staged or enqueued
+    HB_TRY(get_keyset(c, keyset_id, &coin_ks));
+    if (!coin_ks->master) return fail(c, HBTC_ERR_ARG, "key set has no master key (hbtc_keyset_set_master)");
+    if (group != 2 || t == 0) return fail(c, HBTC_ERR_ARG, "t must be >= 1");
+  }
   const size_t pt = group == 1 ? 48 : 96;
   const int l = (c->lane + 1) % hbtc_ctx::NL;
   hbtc_ctx::Ticket& T = c->tickets[l];
@@ -1610,8 +1751,12 @@ int epoch_submit(hbtc_ctx* c, int group, uint32_t keyset_id, uint32_t n_inst, co
       HB_TRY(ws(c, "ep.out", pt * n_inst, &d_out));
       if (group == 2) HB_TRY(ws(c, "ep.par", n_inst, &d_par));
       HB_TRY(ws(c, "ep.cst", 4 * (size_t)n_inst, &d_cst));
-      HB_TRY(combine_dev(c, group, n_inst, offsets, (const uint32_t*)d_idx, (const uint8_t*)d_items, t,
-                         (uint8_t*)d_out, (uint8_t*)d_par, (int32_t*)d_cst, (const int32_t*)d_st));
+      if (coin)
+        HB_TRY(coin_combine_dev(c, coin_ks, n_inst, offsets, n, (const uint32_t*)d_idx, (const uint8_t*)d_items,
+                                t, (const int32_t*)d_st, (uint8_t*)d_out, (uint8_t*)d_par, (int32_t*)d_cst));
+      else
+        HB_TRY(combine_dev(c, group, n_inst, offsets, (const uint32_t*)d_idx, (const uint8_t*)d_items, t,
+                           (uint8_t*)d_out, (uint8_t*)d_par, (int32_t*)d_cst, (const int32_t*)d_st));
       if (sV)
         HB_TRY(dec_pad_dev(c, c->s_comb, n_inst, (const uint8_t*)d_out, (const int32_t*)d_cst, nullptr,
                            v_off, (const uint8_t*)d_v, (uint8_t*)d_plain));
@@ -1660,6 +1805,7 @@ void keyset_release(Keyset& ks) {
   (void)hipFree(ks.last_bad);
   (void)hipFree(ks.rejects);
   (void)hipFree(ks.master);
+  (void)hipFree(ks.master_c48);
   (void)hipFree(ks.c48);
   ks = Keyset();
 }
@@ -1685,6 +1831,17 @@ int keyset_tables(hbtc_ctx* c, Keyset& ks) {
   Fq* tab_ws;
   HB_TRY(wst(c, "pktab.ws", (size_t)n * PK_TAB_WIN * 512, &tab_ws));
   return timed(c, "prepare", [&] { return launch_pk_table(c->stream, ks.pk, ks.st, n, ks.tab, tab_ws); });
+}
+
+// The canonical compressed bytes of a key set's decoded master key (Keyset::master_c48), written
+// by the library's own encoder on the current stream; the caller's sync completes it.
+int keyset_master_c48(hbtc_ctx* c, Keyset& ks) {
+  if (!ks.master_c48) HB_CHECK(c, hipMalloc(&ks.master_c48, 48));
+  int32_t* d_ok;
+  HB_TRY(wst(c, "ks.accept", 1, &d_ok));
+  HB_CHECK(c, launch_zero_u32(c->stream, reinterpret_cast<uint32_t*>(d_ok), 1));  // HBTC_ACCEPT
+  HB_CHECK(c, launch_sv_pk_c48(c->stream, 1, ks.master, d_ok, ks.master_c48));
+  return HBTC_OK;
 }
 
 uint32_t keyset_register(hbtc_ctx* c, const Keyset& ks) {
@@ -1824,6 +1981,7 @@ void hbtc_ctx_destroy(hbtc_ctx* c) {
     (void)hipFree(kv.second.last_bad);
     (void)hipFree(kv.second.rejects);
     (void)hipFree(kv.second.master);
+    (void)hipFree(kv.second.master_c48);
     (void)hipFree(kv.second.c48);
   }
   for (Span& sp : c->spans) {
@@ -2049,10 +2207,17 @@ int hbtc_keyset_set_master(hbtc_ctx* c, uint32_t keyset_id, const uint8_t* mpk) 
   HB_TRY(sync(c));
   if (ks->master) {
     (void)hipFree(ks->master);
+    (void)hipFree(ks->master_c48);
     ks->master = nullptr;
+    ks->master_c48 = nullptr;
   }
   G1A* d_m;
   HB_CHECK(c, hipMalloc(&d_m, sizeof(G1A)));
+  uint8_t* d_c48 = nullptr;
+  if (hipMalloc(&d_c48, 48) != hipSuccess) {
+    (void)hipFree(d_m);
+    return fail(c, HBTC_ERR_OOM, "hipMalloc master key");
+  }
   int32_t st = -1;
   // every step after the allocation frees d_m on failure (the error paths leaked it)
   const int rc = [&]() -> int {
@@ -2061,20 +2226,25 @@ int hbtc_keyset_set_master(hbtc_ctx* c, uint32_t keyset_id, const uint8_t* mpk) 
     HB_TRY(upload(c, "in0", mpk, 48, &d_in));
     HB_TRY(wst(c, "out0", 1, &d_st));
     HB_CHECK(c, launch_g1_decode(c->stream, (const uint8_t*)d_in, 1, d_m, d_st));
+    // re-encoded from the decoded point: the bytes the combines' encoder gives for an equal sum
+    HB_CHECK(c, launch_sv_pk_c48(c->stream, 1, d_m, d_st, d_c48));
     HB_TRY(download(c, &st, d_st, 4));
     return sync(c);
   }();
   if (rc != HBTC_OK || st != HBTC_ACCEPT) {
     (void)hipFree(d_m);
+    (void)hipFree(d_c48);
     return rc != HBTC_OK ? rc : fail(c, HBTC_ERR_ARG, "master public key fails to decode");
   }
   ks->master = d_m;
+  ks->master_c48 = d_c48;
   return HBTC_OK;
 }
 
 // hbtc.h hbtc_coin_decide: the share checks on the lane stream (sig_shares_dev), the speculative
 // leave-one-out combines and master checks on s_spec beside them, then the commit and the
-// status-driven combine + master check of the instances the speculation missed.
+// status-driven combine + master check of the instances the speculation missed.  Above
+// COMB_SMALL_T shares per combine: the checks, then coin_combine_dev (no speculation).
 int hbtc_coin_decide(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H,
                      const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig, uint32_t t,
                      int32_t* status, uint8_t* sig_out, uint8_t* parity, int32_t* coin_status) {
@@ -2083,7 +2253,7 @@ int hbtc_coin_decide(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uin
   Keyset* ks;
   HB_TRY(get_keyset(c, keyset_id, &ks));
   if (!ks->master) return fail(c, HBTC_ERR_ARG, "key set has no master key (hbtc_keyset_set_master)");
-  if (t == 0 || t > COMB_SMALL_T) return fail(c, HBTC_ERR_ARG, "t must be in 1..64");
+  if (t == 0) return fail(c, HBTC_ERR_ARG, "t must be >= 1");
   uint32_t n;
   HB_TRY(check_offsets(c, n_inst, offsets, &n));
   if (n_inst == 0) return HBTC_OK;
@@ -2095,6 +2265,28 @@ int hbtc_coin_decide(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uin
   HB_TRY(upload(c, "in2", sig, (size_t)96 * n, &d_sig));
   HB_TRY(ws(c, "out0", (size_t)4 * n1, &d_st));
   PinLane pin(c);  // the uploads above went to the current lane
+  if (t > COMB_SMALL_T) {
+    // no leave-one-out speculation above the one-workgroup combines: the checks, then the
+    // status-driven Pippenger pair and the device merge (coin_combine_dev), one host wait at the end
+    uint8_t *d_so, *d_pa;
+    int32_t* d_coin;
+    HB_TRY(wst(c, "coin.sig", (size_t)96 * n_inst, &d_so));
+    HB_TRY(wst(c, "coin.par", n_inst, &d_pa));
+    HB_TRY(wst(c, "coin.final", n_inst, &d_coin));
+    {
+      HostG2Args hg(c, d_H, H);
+      HB_TRY(sig_shares_dev(c, keyset_id, n_inst, (const uint8_t*)d_H, offsets, (const uint32_t*)d_idx,
+                            (const uint8_t*)d_sig, (int32_t*)d_st));
+    }
+    HB_TRY(coin_combine_dev(c, ks, n_inst, offsets, n, (const uint32_t*)d_idx, (const uint8_t*)d_sig, t,
+                            (const int32_t*)d_st, d_so, d_pa, d_coin));
+    HB_TRY(stream_after(c, c->stream, c->s_comb, c->ev_comb));
+    HB_TRY(download(c, status, d_st, (size_t)4 * n));
+    HB_TRY(download(c, sig_out, d_so, (size_t)96 * n_inst));
+    HB_TRY(download(c, parity, d_pa, n_inst));
+    HB_TRY(download(c, coin_status, d_coin, (size_t)4 * n_inst));
+    return sync(c);
+  }
   void* p;
   HB_TRY(stage_upload(c, "coin.offsets", offsets, ((size_t)n_inst + 1) * 4, c->stream, &p));
   const uint32_t* d_off = static_cast<const uint32_t*>(p);
@@ -2667,6 +2859,20 @@ int hbtc_sig_epoch_submit(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, cons
     return fail(c, HBTC_ERR_ARG, "NULL combine output");
   return epoch_submit(c, 2, keyset_id, n_inst, H_c96, nullptr, offsets, idx, sig_c96, t, status, out_sig_c96,
                       out_parity, inst_status, ticket);
+}
+
+int hbtc_coin_epoch_submit(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H_c96,
+                           const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_c96, uint32_t t,
+                           int32_t* status, uint8_t* out_sig_c96, uint8_t* out_parity, int32_t* coin_status,
+                           uint64_t* ticket) {
+  if (!c || !ticket || (n_inst && (!H_c96 || !offsets || !out_sig_c96 || !out_parity || !coin_status)))
+    return HBTC_ERR_ARG;
+  Guard g(c);
+  uint32_t n;
+  HB_TRY(check_offsets(c, n_inst, offsets, &n));
+  if (n && (!idx || !sig_c96 || !status)) return fail(c, HBTC_ERR_ARG, "NULL item array");
+  return epoch_submit(c, 2, keyset_id, n_inst, H_c96, nullptr, offsets, idx, sig_c96, t, status, out_sig_c96,
+                      out_parity, coin_status, ticket, nullptr, nullptr, nullptr, true);
 }
 
 int hbtc_wait(hbtc_ctx* c, uint64_t ticket) {
@@ -4158,6 +4364,7 @@ int hbtc_skg_generate(hbtc_ctx* c, uint32_t n_parts, uint32_t t, const uint8_t* 
     if (out_keyset_id) {
       HB_TRY(keyset_tables(c, ks));
       HB_CHECK(c, hipMemcpyAsync(ks.master, d_caff, sizeof(G1A), hipMemcpyDeviceToDevice, c->stream));
+      HB_TRY(keyset_master_c48(c, ks));
     }
     HB_TRY(span_end(c, whole, "keygen"));
     HB_TRY(download(c, h_out.data(), d_out, out_bytes));

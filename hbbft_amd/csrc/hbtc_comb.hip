@@ -479,4 +479,79 @@ hipError_t launch_coin_commit(hipStream_t s, uint32_t n_inst, uint32_t t, const 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- coin calls: t > COMB_SMALL_T
+// The points of the master check's MSM, sum l_i pk_i over a combine's selection: one thread per
+// selected term, by NODE index (sel_idx), not by item position -- out[k * t + i] is the key
+// set's decoded share of the node that sent instance k's i-th selected item.  Reads the decoded
+// shares only (a key set's table entries exist only for keys that loaded).  A selected item is
+// ACCEPT, so its node is in the key set and its key decoded; the slots past sel_cnt (k_select's
+// fillers) and any index past the key set are the point at infinity.
+__global__ void __launch_bounds__(256) k_coin_gather_pk(uint64_t terms, uint32_t t,
+                                                        const uint32_t* __restrict__ sel_idx,
+                                                        const uint32_t* __restrict__ sel_cnt,
+                                                        const G1A* __restrict__ pk, uint32_t n_nodes,
+                                                        G1A* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= terms) return;
+  const uint32_t k = (uint32_t)(g / t), i = (uint32_t)(g % t);
+  const uint32_t node = sel_idx[g];
+  G1A p;
+  if (i < sel_cnt[k] && node < n_nodes) {
+    p = pk[node];
+  } else {
+    fzero(p.x);
+    fzero(p.y);
+    p.inf = 1;
+  }
+  out[g] = p;
+}
+
+hipError_t launch_coin_gather_pk(hipStream_t s, uint32_t n_inst, uint32_t t, const uint32_t* sel_idx,
+                                 const uint32_t* sel_cnt, const G1A* pk, uint32_t n_nodes, G1A* out) {
+  const uint64_t terms = (uint64_t)n_inst * t;
+  if (terms == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_coin_gather_pk, dim3((uint32_t)((terms + 255) / 256)), dim3(256), 0, s, terms, t,
+                     sel_idx, sel_cnt, pk, n_nodes, out);
+  return hipGetLastError();
+}
+
+// The coin status of every instance, one thread each: the combine's failure if there is one, else
+// the master check.  master_st (the small combines' cmp result, ACCEPT / REJECT) when given; else
+// sum_c48[k], the compressed sum l_i pk_i of the Pippenger route, against master_c48 -- as
+// canonical compressed BYTES, both written by the library's own encoder from decoded points, so
+// equal bytes are equal points and nothing else is.
+__global__ void __launch_bounds__(64) k_coin_final(uint32_t n_inst, const int32_t* __restrict__ cst,
+                                                   const int32_t* __restrict__ master_st,
+                                                   const uint8_t* __restrict__ sum_c48,
+                                                   const uint8_t* __restrict__ master_c48,
+                                                   int32_t* __restrict__ coin_status) {
+  const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n_inst) return;
+  int32_t st = cst[k];
+  if (st == HBTC_ACCEPT) {
+    if (master_st) {
+      st = master_st[k];
+    } else {
+      const uint4* a = reinterpret_cast<const uint4*>(sum_c48 + (size_t)k * 48);
+      const uint4* b = reinterpret_cast<const uint4*>(master_c48);
+      uint32_t diff = 0;
+      for (int j = 0; j < 3; ++j) {
+        const uint4 x = a[j], y = b[j];
+        diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+      }
+      st = diff ? HBTC_REJECT : HBTC_ACCEPT;
+    }
+  }
+  coin_status[k] = st;
+}
+
+hipError_t launch_coin_final(hipStream_t s, uint32_t n_inst, const int32_t* cst, const int32_t* master_st,
+                             const uint8_t* sum_c48, const uint8_t* master_c48, int32_t* coin_status) {
+  if (n_inst == 0) return hipSuccess;
+  if (!master_st && (!sum_c48 || !master_c48)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_coin_final, dim3((n_inst + 63) / 64), dim3(64), 0, s, n_inst, cst, master_st,
+                     sum_c48, master_c48, coin_status);
+  return hipGetLastError();
+}
+
 }  // namespace hbtc

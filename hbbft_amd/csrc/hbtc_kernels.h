@@ -396,6 +396,14 @@ hipError_t launch_coin_commit(hipStream_t s, uint32_t n_inst, uint32_t t, const 
                               const uint8_t* spec_sig, const uint8_t* spec_par,
                               const int32_t* spec_master, int32_t* cst, uint8_t* sig, uint8_t* par,
                               int32_t* master, uint32_t* redo);
+// coin rounds of t > COMB_SMALL_T (hbtc_comb.hip): the master check's MSM points, the key set's
+// decoded shares pk[sel_idx] by node index (infinity past sel_cnt or n_nodes), and the merged
+// per-instance coin status -- cst's failure, else master_st (when given), else ACCEPT / REJECT
+// from sum_c48[k] == master_c48 as canonical compressed bytes
+hipError_t launch_coin_gather_pk(hipStream_t s, uint32_t n_inst, uint32_t t, const uint32_t* sel_idx,
+                                 const uint32_t* sel_cnt, const G1A* pk, uint32_t n_nodes, G1A* out);
+hipError_t launch_coin_final(hipStream_t s, uint32_t n_inst, const int32_t* cst, const int32_t* master_st,
+                             const uint8_t* sum_c48, const uint8_t* master_c48, int32_t* coin_status);
 
 // ---- SyncKeyGen (hbtc_skg.hip)
 hipError_t launch_skg_sym_scalars(hipStream_t s, uint32_t n_parts, uint32_t M, const Fr* U,

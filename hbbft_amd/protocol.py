@@ -20,7 +20,9 @@ by ONE ctx.decrypt_shares call (SecretKeyShare::decrypt_share, td.rs:98: H, Ciph
 and sk u); ``own_share(key)`` is the share to multicast.  ThresholdDecryption outputs the combined point
 g = sum l_i d_i (compressed) by default; DecryptionEpoch(plaintext=True) outputs what the
 reference's try_output does, the plaintext v XOR hash_bytes(g, |v|), made on the GPU behind the
-combine (hbtc_threshold_decrypt).
+combine (hbtc_threshold_decrypt).  CoinEpoch(decide=True) sends a flush through ONE
+ctx.coin_decide call (checks, combine, master check) and keeps that call's result for every
+instance whose deferred combine would take exactly the items the call selected.
 """
 from . import _native as N
 
@@ -56,14 +58,49 @@ class _CoinState:
         self.terminated = False
 
 
-class CoinEpoch:
-    """Every Coin instance (coin.rs:64) of one epoch behind one batch queue."""
+def coin_call_selection(counts, idx, sigs, status, t):
+    """What one coin_decide call combined, worked out on the host from its item statuses: per
+    instance the first t ACCEPTed items in call order as a frozenset of (node index, share
+    bytes), or None when the instance has fewer than t of them."""
+    sel, pos = [], 0
+    for c in counts:
+        acc = [j for j in range(pos, pos + c) if int(status[j]) == N.ACCEPT][:t]
+        sel.append(frozenset((int(idx[j]), bytes(sigs[j])) for j in acc) if len(acc) == t else None)
+        pos += c
+    return sel
 
-    def __init__(self, ctx, netinfo, *, sk_share=None):
+
+def coin_call_serves(selected, items, t):
+    """Whether the call's result for an instance is the deferred combine's: `items` is what
+    _try_output hands the combine (node index, share), sorted by node index; the combine takes
+    its first t.  True when those are exactly the t distinct items the call selected -- shares
+    carried over from an earlier flush, an input after more than t shares, or a repeated sender
+    make the two differ (or the selection hold fewer than t distinct items)."""
+    if selected is None or len(selected) != t or len(items) < t:
+        return False
+    return frozenset((int(i), bytes(s)) for i, s in items[:t]) == selected
+
+
+class CoinEpoch:
+    """Every Coin instance (coin.rs:64) of one epoch behind one batch queue.
+
+    decide=False (the default): a flush is ctx.verify_sig_shares, then one combine_sigs and one
+    verify_sigs for the instances that reach their threshold.  decide=True, with the NetInfo's
+    master_pk: the flush sends the same items through ONE ctx.coin_decide call, and an instance
+    whose deferred combine would take exactly the items that call selected uses the call's
+    result; any other instance goes through the combine as before.  `decided` and `fallback`
+    count the instances that took each path."""
+
+    def __init__(self, ctx, netinfo, *, sk_share=None, decide=False):
         self.ctx = ctx
         self.ni = netinfo
         self.inst = {}
         self.sk_share = sk_share
+        self.decide = bool(decide) and netinfo.master_pk is not None
+        self.decided = 0
+        self.fallback = 0
+        if self.decide:  # once: the key set keeps the decoded master key resident
+            ctx.keyset_set_master(netinfo.keyset, netinfo.master_pk)
 
     def add(self, key, H_c96=None, our_share_c96=None, nonce=None):
         """H_c96 (and our_share_c96 for a validator) from the caller, or, with sk_share set,
@@ -130,15 +167,22 @@ class CoinEpoch:
                     c += 1
             counts.append(c)
         verdict = {}
+        call = {}  # decide: per instance (the call's selection, coin status, parity)
         if idx:
-            status = self.ctx.verify_sig_shares(ni.keyset, [self.inst[k].H for k in keys], counts,
-                                                idx, sigs)
+            Hs = [self.inst[k].H for k in keys]
+            if self.decide:
+                t = ni.num_faulty + 1
+                status, _, par, cst = self.ctx.coin_decide(ni.keyset, Hs, counts, idx, sigs, t)
+                sel = coin_call_selection(counts, idx, sigs, status, t)
+                call = {k: (sel[j], int(cst[j]), bool(par[j])) for j, k in enumerate(keys)}
+            else:
+                status = self.ctx.verify_sig_shares(ni.keyset, Hs, counts, idx, sigs)
             for key_ev, pos in where.items():
                 verdict[key_ev] = int(status[pos]) == N.ACCEPT
         results, pending = {}, []
         for k in keys:
             results[k] = self._replay(k, verdict, pending)
-        self._finish_combines(pending, results, verdict, snap)
+        self._finish_combines(pending, results, verdict, snap, call)
         for k in keys:
             self.inst[k].events = []
         return results
@@ -213,10 +257,27 @@ class CoinEpoch:
                 res[j] = (None, bool(par[j]))
         return res
 
-    def _finish_combines(self, pending, results, verdict, snap):
+    def _finish_combines(self, pending, results, verdict, snap, call=None):
         if not pending:
             return
-        res = self._combine([p[0] for p in pending], [p[2] for p in pending])
+        t = self.ni.num_faulty + 1
+        res = [None] * len(pending)
+        rest = []
+        for j, (k, e_i, items, step) in enumerate(pending):
+            sel, cst, parity = (call or {}).get(k, (None, None, None))
+            if not coin_call_serves(sel, items, t):
+                rest.append(j)
+            elif cst == N.ACCEPT:
+                res[j] = (None, parity)
+            elif cst == N.REJECT:  # the master check of coin.rs:192-197
+                res[j] = ("VerificationFailed", None)
+            else:
+                res[j] = ("CombineAndVerifySigCrypto:%s" % N.STATUS_NAMES[cst], None)
+        self.decided += len(pending) - len(rest)
+        self.fallback += len(rest) if self.decide else 0
+        if rest:
+            for j, r in zip(rest, self._combine([pending[j][0] for j in rest], [pending[j][2] for j in rest])):
+                res[j] = r
         failed = set()
         for (k, e_i, items, step), (err, parity) in zip(pending, res):
             if err is None:

@@ -121,7 +121,9 @@ int hbtc_verify_sigs(hbtc_ctx* ctx, uint32_t n, const uint8_t* pk_c48, const uin
                      const uint8_t* sig_c96, int32_t* status);
 
 /* The key set's master public key (NetworkInfo::public_key, src/messaging.rs:253; compressed
- * G1), decoded once with the subgroup check and kept resident for hbtc_coin_decide.  Returns
+ * G1), decoded once with the subgroup check and kept resident for hbtc_coin_decide /
+ * hbtc_coin_epoch_submit (the point, and its canonical compressed bytes for the comparison of
+ * the large-t rounds).  Returns
  * HBTC_OK, or HBTC_ERR_ARG when it fails to decode (the key set keeps no master key then). */
 int hbtc_keyset_set_master(hbtc_ctx* ctx, uint32_t keyset_id, const uint8_t* master_pk_c48);
 
@@ -154,10 +156,19 @@ int hbtc_prepared_g2_count(hbtc_ctx* ctx, uint32_t* count);
  * in HBTC_MODE_PER_SHARE and for calls below hbtc_set_exact_below (256 shares: every coin of up
  * to N = 255), and otherwise wrong with probability <= 2^-k per RLC group for k-bit scalars
  * (hbtc_set_rlc_bits: 2^-128 by default, the curve's level; 2^-64 when set to 64), where the
- * reference's separate pairing check (coin.rs:192-197) would be exact.  Small calls (n_inst * (t + 1) <= 256, t < 64) combine speculatively while the
+ * reference's separate pairing check (coin.rs:192-197) would be exact.
+ * t <= 64: small calls (n_inst * (t + 1) <= 256, t < 64) combine speculatively while the
  * shares are checked: every leave-one-out subset of each instance's first t + 1 items, committed
  * when the verified selection is one of them (at most one of the first t + 1 rejected), else
- * combined again from the statuses.  Needs hbtc_keyset_set_master; t in 1..64. */
+ * combined again from the statuses.
+ * t > 64 (no limit on N): no speculation.  Behind the share checks, on the same lane, the first t
+ * ACCEPTed items of every instance are selected and their Lagrange coefficients computed ONCE;
+ * the G2 Pippenger combine over the shares and then a G1 Pippenger combine over the key set's
+ * resident shares of the same nodes (gathered by node index) read that one selection, and the
+ * sum is compared on the device with the master key as canonical compressed bytes.  Statuses are
+ * those of hbtc_verify_sig_shares + hbtc_combine_sigs + hbtc_verify_sigs composed; the soundness
+ * statement above holds unchanged (the same identity, the same share checks under it).
+ * Needs hbtc_keyset_set_master (else HBTC_ERR_ARG); t >= 1. */
 int hbtc_coin_decide(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H_c96,
                      const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_items_c96,
                      uint32_t t, int32_t* status, uint8_t* sig_c96, uint8_t* parity,
@@ -408,6 +419,17 @@ int hbtc_sig_epoch_submit(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_inst, co
                           const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_c96,
                           uint32_t t, int32_t* status, uint8_t* out_sig_c96, uint8_t* out_parity,
                           int32_t* inst_status, uint64_t* ticket);
+/* hbtc_sig_epoch_submit plus the master check: hbtc_coin_decide without blocking, on the next
+ * lane, inputs and results through the ticket's pinned staging, collected by hbtc_wait with no
+ * host wait in between.  status / out_sig_c96 / out_parity / coin_status are hbtc_coin_decide's;
+ * coin_status is merged on the device (the combine's failure, else ACCEPT / REJECT from the master
+ * check).  Any t >= 1: up to 64 the status-driven one-workgroup combines (no speculation), above
+ * the Pippenger path of hbtc_coin_decide.  HBTC_ERR_ARG, with nothing enqueued, for a key set
+ * without a master key (hbtc_keyset_set_master) or t == 0.  The same four-in-flight rule. */
+int hbtc_coin_epoch_submit(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_inst, const uint8_t* H_c96,
+                           const uint32_t* offsets, const uint32_t* idx, const uint8_t* sig_c96,
+                           uint32_t t, int32_t* status, uint8_t* out_sig_c96, uint8_t* out_parity,
+                           int32_t* coin_status, uint64_t* ticket);
 int hbtc_wait(hbtc_ctx* ctx, uint64_t ticket);
 
 /* ---- batched scalar multiplication -------------------------------------------------------- */
