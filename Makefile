@@ -163,7 +163,7 @@ resources-rlc:
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"; done
 
 # the MSM kernels (k_msm_buckets and its neighbours) with the flags of hbtc_msm.p8.o / p9.o;
-# MSM_FLAGS=-DHBTC_MSM_WALK=0 reports the nested-loop walk
+# MSM_FLAGS=-DHBTC_MSM_WALK=0 reports the nested-loop walk, -DHBTC_FQ_RR=3 the walk on 12 x 32
 .PHONY: resources-msm
 resources-msm:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_PART=8 -DHBTC_FQMUL_INLINE -DHBTC_INLINE_ALL $(MSM_FLAGS) -c $(CSRC)/hbtc_msm.hip -o /dev/null \
@@ -201,7 +201,7 @@ hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so 
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
           tests/native/libhbtc_own_hosttest.so tests/native/libhbtc_msm_hosttest.so \
           tests/native/libhbtc_rr_hosttest.so tests/native/libhbtc_rrw_hosttest.so \
-          tests/native/libhbtc_xadicw_hosttest.so
+          tests/native/libhbtc_xadicw_hosttest.so tests/native/libhbtc_msmw_hosttest.so
 # the 13 x 30 Fq code's host build (field.h FqR over fq_rr.h's plain 64-bit schedule, every MAD
 # checked for a carry-out) and the G1 decode with its square root on it
 tests/native/libhbtc_rr_hosttest.so: tests/native/hbtc_rr_hosttest.cpp tests/native/hbtc_rr_ops.h $(HDRS)
@@ -238,6 +238,10 @@ sanitize-xadicw: | $(BUILD)
 # and over G1)
 tests/native/libhbtc_msm_hosttest.so: tests/native/hbtc_msm_hosttest.cpp $(HDRS)
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_msm_hosttest.cpp -o $@
+# the G1 bucket walk over JacW (k_msm_buckets<Fq> under HBTC_MSM_WALKW) in lockstep beside the 12 x 32
+# walk, both bounds of every FqW tracked and asserted at every operation
+tests/native/libhbtc_msmw_hosttest.so: tests/native/hbtc_msmw_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_msmw_hosttest.cpp -o $@
 # the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
 .PHONY: sanitize-msm
 sanitize-msm: | $(BUILD)

@@ -1323,6 +1323,22 @@ HD void jacw_add(JacW& r, const JacW& p, const JacW& q) {
   fw_mul(z3, z3, H);
   jacw_add_tail(r, u1, s1, H, HH, rr0, z3);
 }
+// The names msm_walk.h calls on its point type J (the bucket walk of hbtc_msm.hip over JacW)
+HD void jac_set_inf(JacW& r) { jacw_set_inf(r); }
+HD void jac_dbl(JacW& r, const JacW& p) { jacw_dbl(r, p); }
+HD void jac_add(JacW& r, const JacW& p, const JacW& q) { jacw_add(r, p, q); }
+// r = p + q for a 12 x 32 Montgomery affine term as the point sets hold it (q.inf allowed): the two
+// coordinates go into the R' domain at the step (2 products), so q is a product result below 1.5p
+// as jacw_add_aff's closure takes it.  A negated term is negated by the caller on 12 x 32 (< 2p).
+HD void jacw_add_g1a(JacW& r, const JacW& p, const G1A& q) {
+  if (q.inf) {
+    r = p;
+    return;
+  }
+  AffW qw;
+  affw_from_aff(qw, q);
+  jacw_add_aff(r, p, qw);
+}
 // Is p (not infinity) the affine point (ax, ay)?  Both sides as product results, compared as
 // canonical residues.  ax, ay weakly normalised.
 HD bool jacw_eq_aff(const JacW& p, const FqW& ax, const FqW& ay) {

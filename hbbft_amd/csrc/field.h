@@ -73,10 +73,11 @@
 // The product and squaring on 13 limbs of 30 bits (tools/gen_fq_rr.py): no carry word per MAC.
 // HBTC_FQ_RR=1 runs the square root of k_rlc_decode's G1 decode on it (FqR below); 2 also runs the
 // two |x| chains of that kernel's subgroup test on its redundant form (FqW below, curve.h jacw_*);
-// 3 also runs k_rlc_items' x-adic multiplication there (curve.h xadic_mul_sac8_w); 0 builds the
+// 3 also runs k_rlc_items' x-adic multiplication there (curve.h xadic_mul_sac8_w); 4 also runs the
+// G1 bucket walk of the Pippenger reduction there (hbtc_msm.hip HBTC_MSM_WALKW); 0 builds the
 // 12 x 32 code everywhere, for comparisons.
 #ifndef HBTC_FQ_RR
-#define HBTC_FQ_RR 3
+#define HBTC_FQ_RR 4
 #endif
 #include "fq_rr.h"
 

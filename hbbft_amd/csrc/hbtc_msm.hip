@@ -33,6 +33,8 @@
 //   roff   [m][w][r]      u32 start of bucket rank r (rank 0 = bucket 2^(c-1)), r = 0..B
 //   part   [m][w][s]      Jac<F> segment partial sums;  wsum [m][w] Jac<F>
 #include "hbtc_kernels.h"
+#include <type_traits>
+
 #include "msm_walk.h"
 #include "pair.h"
 
@@ -485,6 +487,12 @@ __device__ __forceinline__ void msm_generator(G2A& p) {
 #ifndef HBTC_MSM_BUCKET_WAVES
 #define HBTC_MSM_BUCKET_WAVES 2
 #endif
+// The G1 bucket walk on the redundant 13 x 30 form (curve.h JacW): run, tot and the snapshot slot are
+// JacW, the term goes into the R' domain at the step, tot leaves through jacw_to_jac.  Part of
+// HBTC_FQ_RR=4; 0 keeps the 12 x 32 walk (variant builds).
+#ifndef HBTC_MSM_WALKW
+#define HBTC_MSM_WALKW (HBTC_FQ_RR >= 4 && HBTC_MSM_WALK)
+#endif
 template <class F, int NW>
 __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_DECODE_WAVES : 1))
     k_msm_decode(uint32_t n_inst, uint32_t t, uint32_t stride,
@@ -579,6 +587,13 @@ __device__ __forceinline__ void msm_walk_flush(MsmWalk& w, J& tot, const St& st)
   for (uint32_t k = 0; k < MSM_SLOTS && __any(walk_pending(w) > k); ++k) walk_flush(w, k, tot, st);
   walk_flush_done(w);
 }
+// The step and the exit of the walk for each point type: run += q, part = tot
+template <class F>
+__device__ __forceinline__ void msm_walk_add(Jac<F>& run, const Aff<F>& q) { jac_add_aff(run, run, q); }
+template <class F>
+__device__ __forceinline__ void msm_walk_store(Jac<F>& part, const Jac<F>& tot) { part = tot; }
+__device__ __forceinline__ void msm_walk_add(JacW& run, const G1A& q) { jacw_add_g1a(run, run, q); }
+__device__ __forceinline__ void msm_walk_store(G1J& part, const JacW& tot) { jacw_to_jac(part, tot); }
 #endif
 
 // One lane per (msm, window, segment): S = B/8 segments split the window's sorted nonzero terms
@@ -609,9 +624,15 @@ __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_BUCKET
 #if HBTC_MSM_WALK
   // the lane-uniform walk (msm_walk.h): one loop over the slice's positions, rank boundaries
   // deferred through the lane's snapshot slots in LDS, the wave flushing together
-  __shared__ uint32_t snap[MSM_SLOTS * WalkLds<Jac<F>>::NW * 64];
-  WalkLds<Jac<F>> st{snap + threadIdx.x};
-  Jac<F> run, tot;
+#if HBTC_MSM_WALKW
+  // G1: the walk's points on the redundant 13 x 30 form (39 words a snapshot slot)
+  typedef typename std::conditional<std::is_same<F, Fq>::value, JacW, Jac<F>>::type WJ;
+#else
+  typedef Jac<F> WJ;
+#endif
+  __shared__ uint32_t snap[MSM_SLOTS * WalkLds<WJ>::NW * 64];
+  WalkLds<WJ> st{snap + threadIdx.x};
+  WJ run, tot;
   jac_set_inf(run);
   jac_set_inf(tot);
   MsmWalk w;
@@ -628,11 +649,12 @@ __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_BUCKET
       const uint32_t v = L[walk_step(w)];
       Aff<F> q = P[v & 0x7fffffffu];
       if (v >> 31) fneg(q.y, q.y);
-      jac_add_aff(run, run, q);
+      msm_walk_add(run, q);
     }
   }
   msm_walk_flush(w, tot, st);
   walk_finish(tot, run, w, B);
+  msm_walk_store(part[g], tot);
 #else
   Jac<F> run, tot;
   jac_set_inf(run);
@@ -660,8 +682,8 @@ __global__ void __launch_bounds__(64, (sizeof(F) == sizeof(Fq) ? HBTC_MSM_BUCKET
       jac_add(tot, tot, m);
     }
   }
-#endif
   part[g] = tot;
+#endif
 }
 
 template <class F>

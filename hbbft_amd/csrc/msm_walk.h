@@ -21,7 +21,8 @@
 // tot += snapshot[k] together.  One more flush follows the loop, then the multiple of run.
 //
 // The pieces below are the per-lane state machine (begin, boundary, step, flush, finish) over any
-// group that provides jac_set_inf / jac_add / jac_dbl on its point type J; the snapshot store is a
+// group that provides jac_set_inf / jac_add / jac_dbl on its point type J (Jac<F>, the lane-pair
+// G2Jp, and curve.h's JacW for the G1 walk on 30-bit limbs); the snapshot store is a
 // policy with put(k, J) / get(J, k); the caller owns the loop, loads the terms and takes the wave
 // vote (the only device-only piece: `any lane needs a flush`, `any lane has positions left`):
 //

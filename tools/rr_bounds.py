@@ -15,6 +15,8 @@ check_closure() shows that from the declared loop-entry bound ENTRY every output
 both additions, with and without the special-case exits, is inside ENTRY again.
 check_items_closure() does the same for the item pass's x-adic multiplication (curve.h
 xadic_mul_sac8_w): the packed table chain, the column, the even-d0 correction and the exit.
+check_walk_closure() runs the calls of the G1 bucket walk (hbtc_msm.hip k_msm_buckets<Fq> over JacW) in
+the walk's order: the step, the flush, walk_finish and the exit.
 
 Usage: tools/rr_bounds.py            (prints the bound of every output and "closure ok")
 """
@@ -498,8 +500,49 @@ def check_items_closure(verbose=False):
     return True
 
 
+def check_walk_closure(verbose=False):
+    """The G1 bucket walk over JacW (hbtc_msm.hip k_msm_buckets<Fq>, msm_walk.h).  Every point the walk
+    holds -- run, tot, a snapshot -- starts as jacw_set_inf and is only ever the output of one of the
+    three formulas, so it is enough that each call maps the entry bound into itself on every exit:
+      the step      run = jacw_add_aff(run, q), q = fw_from_fq of a 12 x 32 coordinate below 2p (a negated
+                    term is negated before the conversion): a product result below 1.5p.  On the exit for
+                    run = infinity the output is (q.x, q.y, 1);
+      the flush     tot = jacw_add(tot, snapshot), the snapshot a stored value of run;
+      walk_finish   acc = run; acc = jacw_dbl(acc); acc = jacw_add(acc, run); tot = jacw_add(tot, acc);
+      the exit      jacw_to_jac: each coordinate times the constant K_OUT, a product of an operand inside
+                    the relaxed blocks' bound, and the result below 2p as part[] holds it.
+    The first three are the calls check_closure() covers (add_aff with an affine product result, add with
+    a base inside the entry bound, dbl); they are run here again in the walk's order, on every exit."""
+    ent = entry()
+    q = (strict(PACK_V), strict(PACK_V))
+    for forced in paths():
+        o = Bounds(forced)
+        inf = jacw_set_inf(o)
+        for run in (inf, (ent, ent, ent)):
+            for tot in (inf, (ent, ent, ent)):
+                step = jacw_add_aff(o, run, q)
+                flush = jacw_add(o, tot, step)
+                acc = jacw_add(o, jacw_dbl(o, step), step)
+                fin = jacw_add(o, flush, acc)
+                worst = jacw_add(o, jacw_add(o, tot, run), jacw_add(o, jacw_dbl(o, run), run))  # from the bound itself
+                for name, out in (("step", step), ("flush", flush), ("finish", acc), ("total", fin), ("entry", worst)):
+                    for c, b in zip("XYZ", out):
+                        if verbose and not forced and run[0] is ent and tot[0] is ent:
+                            print("walk %-6s %s: %r" % (name, c, b))
+                        if not b.within(ent):
+                            raise BoundsError("walk %s %s leaves the entry bound on path %s: %r" % (name, c, forced, b))
+    o = Bounds()
+    kout = o.const(G.K_OUT * pow(G.ONE, -1, P) % P)
+    for b in (o.mul(ent, kout),):
+        if max(b.l) > M or b.v >= 2:
+            raise BoundsError("walk exit is not a product result below 2p: %r" % (b,))
+    return True
+
+
 if __name__ == "__main__":
     check_closure(verbose=True)
     print("closure ok: entry %r" % entry())
+    check_walk_closure(verbose=True)
+    print("bucket walk: step, flush, finish and exit ok")
     check_items_closure(verbose=True)
     print("item pass: table chain, column, correction and exit ok")
