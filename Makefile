@@ -21,7 +21,7 @@ KOBJS := $(foreach p,$(PARTS),$(BUILD)/hbtc_kernels.p$(p).o) $(foreach p,$(RLC_P
          $(foreach p,$(MSM_PARTS),$(BUILD)/hbtc_msm.p$(p).o) $(foreach p,$(SKG_PARTS),$(BUILD)/hbtc_skg.p$(p).o) \
          $(BUILD)/hbtc_check.c1.o $(BUILD)/hbtc_check.c2.o $(BUILD)/hbtc_sig.s1.o $(BUILD)/hbtc_sig.s2.o $(BUILD)/hbtc_pb.o \
          $(BUILD)/hbtc_bcast.o $(BUILD)/hbtc_comb.o $(BUILD)/hbtc_enc.o $(BUILD)/hbtc_keygen.o $(BUILD)/hbtc_own.o \
-         $(BUILD)/hbtc_sv.o
+         $(BUILD)/hbtc_sv.o $(BUILD)/hbtc_skgp.o
 LIB := hbbft_amd/libhbtc.so
 
 .PHONY: all lib hosttest devtest oracle clean resources roofline-constants
@@ -133,6 +133,11 @@ $(BUILD)/hbtc_own.o: $(CSRC)/hbtc_own.hip $(HDRS) | $(BUILD)
 $(BUILD)/hbtc_sv.o: $(CSRC)/hbtc_sv.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
 
+# SyncKeyGen::new's Part and the Acks (k_skgp_commit, k_skgp_rows, k_skgp_vals: the stages in front of
+# the encryption's): the flag set of hbtc_enc.o (`make resources-skgp` prints the resource report)
+$(BUILD)/hbtc_skgp.o: $(CSRC)/hbtc_skgp.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $< -o $@
+
 # Reliable Broadcast: Reed-Solomon over GF(2^8), SHA3 Merkle trees and proofs
 $(BUILD)/hbtc_bcast.o: $(CSRC)/hbtc_bcast.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -176,6 +181,12 @@ resources-enc:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_enc.hip -o /dev/null \
 	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill"
 
+# the SyncKeyGen producer's kernels, and hbtc_enc.hip again for k_enc_g1_rcpt beside k_enc_g1
+.PHONY: resources-skgp
+resources-skgp:
+	for f in hbtc_skgp hbtc_enc; do $(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/$$f.hip -o /dev/null \
+	  -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|AGPRs|Scratch|Occupancy|Spill|LDS"; done
+
 .PHONY: resources-keygen
 resources-keygen:
 	$(HIPCC) $(HIPFLAGS) -DHBTC_INLINE_ALL -DHBTC_FQMUL_SR -c $(CSRC)/hbtc_keygen.hip -o /dev/null \
@@ -201,7 +212,18 @@ hosttest: tests/native/libhbtc_hosttest.so tests/native/libhbtc_enc_hosttest.so 
           tests/native/libhbtc_keygen_hosttest.so tests/native/libhbtc_tree_hosttest.so \
           tests/native/libhbtc_own_hosttest.so tests/native/libhbtc_msm_hosttest.so \
           tests/native/libhbtc_rr_hosttest.so tests/native/libhbtc_rrw_hosttest.so \
-          tests/native/libhbtc_xadicw_hosttest.so tests/native/libhbtc_msmw_hosttest.so
+          tests/native/libhbtc_xadicw_hosttest.so tests/native/libhbtc_msmw_hosttest.so \
+          tests/native/libhbtc_skgp_hosttest.so
+# skgp.h's host build (the SyncKeyGen producer's item bodies: the paired commitment, the triangle
+# Horner, the Poly and FieldWrap frames)
+tests/native/libhbtc_skgp_hosttest.so: tests/native/hbtc_skgp_hosttest.cpp $(HDRS)
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -I$(CSRC) tests/native/hbtc_skgp_hosttest.cpp -o $@
+# the same as a stand-alone program under AddressSanitizer and UBSan: host code only, run on the CPU
+.PHONY: sanitize-skgp
+sanitize-skgp: | $(BUILD)
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) \
+	  tests/native/hbtc_skgp_host_main.cpp tests/native/hbtc_skgp_hosttest.cpp -o $(BUILD)/skgp_host_asan
+	$(BUILD)/skgp_host_asan
 # the 13 x 30 Fq code's host build (field.h FqR over fq_rr.h's plain 64-bit schedule, every MAD
 # checked for a carry-out) and the G1 decode with its square root on it
 tests/native/libhbtc_rr_hosttest.so: tests/native/hbtc_rr_hosttest.cpp tests/native/hbtc_rr_ops.h $(HDRS)

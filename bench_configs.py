@@ -35,6 +35,8 @@ checked against the construction after timing:
       Parts (N evaluations and N encryptions each, :371-380).  Host buffers and the Python
       framing are inside the timed region; sampled recipients decrypt their row and values after
       timing and check them against the commitment and the rows.
+  c5p1 The c5p workload through SyncKeyGen.new(..., one_call=True): the Part by hbtc_skg_part and
+      the Acks by hbtc_skg_acks, the recipients a key set loaded once per step; the same checks.
   kg  The end of a SyncKeyGen era at N = --nodes, t = (N - 1) / 3 (not in the default list): one
       generate_keys() of hbbft_amd/skg.py over t + 1 complete Parts of t + 1 values each
       (SyncKeyGen::generate + NetworkInfo::new, src/sync_key_gen.rs:428-447, messaging.rs:253-256;
@@ -86,7 +88,7 @@ checked against the construction after timing:
       (shard_len = ceil((value + 4) / (N - 2f))).  Inputs resident in HBM; the outputs are
       compared with the proposals after timing.
 
-Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,kg,bc,td,own,sv,coin] [--steps K] [--warmup W]
+Usage: python bench_configs.py [--configs c1,c2,c4,c5,c5p,c5p1,kg,bc,td,own,sv,coin] [--steps K] [--warmup W]
 """
 import argparse
 import ctypes
@@ -116,7 +118,7 @@ G2_GEN = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bb
                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
 SEED = 0x6862626674
 N_OUT = 6  # output sets rotated per step (bench.py's N_OUT)
-STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "bc": 20, "td": 5, "kg": 3, "own": 7}
+STEPS_DEFAULT = {"c1": 50, "c2": 20, "c4": 6, "c5": 1, "c5p": 1, "c5p1": 1, "bc": 20, "td": 5, "kg": 3, "own": 7}
 
 
 def log(*a):
@@ -757,12 +759,15 @@ def bench_skg(ctx, n, n_parts, n_distinct, steps, warmup, cpu_budget=0.0):
     }
 
 
-def bench_skg_producer(ctx, n, n_parts, steps, warmup):
+def bench_skg_producer(ctx, n, n_parts, steps, warmup, one_call=False):
     """c5p: one node's SyncKeyGen PRODUCER work at N=n (t = (n-1)/3), through hbbft_amd/skg.py as a
     caller uses it: SyncKeyGen.new (the Part: commitment, n rows, n row encryptions), then the
-    Acks for n_parts valid Parts (n evaluations and n encryptions each)."""
+    Acks for n_parts valid Parts (n evaluations and n encryptions each).  one_call (c5p1): the same
+    through SyncKeyGen.new(..., one_call=True): hbtc_skg_part and hbtc_skg_acks, the recipients'
+    key set loaded in SyncKeyGen.new (inside part_ms) and freed after the step."""
     from hbbft_amd import skg, wire
     rng = random.Random(SEED + 55)
+    name = "c5p1" if one_call else "c5p"
     t = (n - 1) // 3
     sks = [rng.randrange(1, R) for _ in range(n)]
     pk, st = ctx.g1_mul(G1_GEN, fr_bytes(sks))
@@ -775,11 +780,14 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
 
     def step():
         a0 = time.perf_counter()
-        kg, part = skg.SyncKeyGen.new(ctx, our, sks[our], pub, t)
+        kg, part = skg.SyncKeyGen.new(ctx, our, sks[our], pub, t, one_call=True) if one_call else \
+            skg.SyncKeyGen.new(ctx, our, sks[our], pub, t)
         a1 = time.perf_counter()
         out = [None] * n_parts
         kg._emit_acks([(p, p % n, rows[p]) for p in range(n_parts)], out)
         a2 = time.perf_counter()
+        if one_call:
+            kg.close()
         t_part[0] += a1 - a0
         t_acks[0] += a2 - a1
         last["part"], last["acks"] = part, out
@@ -788,7 +796,8 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
         step()
     t_part[0] = t_acks[0] = 0.0
     elapsed = timed_steps(ctx, step, steps, 0)
-    per = breakdown(ctx, steps, ["mul", "hash", "enc_g1", "enc_pad", "enc_w", "fr_poly"])
+    per = breakdown(ctx, steps, ["mul", "hash", "enc_g1", "enc_pad", "enc_w", "fr_poly"] +
+                    (["prepare", "skgp_commit", "skgp_frame", "skg_part", "skg_acks"] if one_call else []))
     # results check against decryption: sampled recipients decrypt their row (checked against the
     # Part's commitment) and their value of sampled Acks (checked against row(j + 1))
     part, acks = last["part"], last["acks"]
@@ -808,7 +817,7 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
             ok = val is not None and wire.fr_value_from_wire(val) == skg._poly_eval(rows[p], j + 1)
             bad += 0 if ok else 1
     if bad:
-        raise SystemExit("c5p: %d decrypted rows / values differ from the construction" % bad)
+        raise SystemExit(name + ": %d decrypted rows / values differ from the construction" % bad)
     n_enc = n + n_parts * n
     return {
         "metric": "SyncKeyGen producer: encryptions/sec (one Part + the Acks of n_parts Parts)",
@@ -817,7 +826,7 @@ def bench_skg_producer(ctx, n, n_parts, steps, warmup):
         "higher_is_better": True, "dtype": "u32 (381-bit Montgomery limbs)",
         "data": "synthetic (random bivariate polynomial, random rows); host buffers (PCIe-inclusive), "
                 "Python framing included",
-        "config": {"workload": "c5p: SyncKeyGen N=%d producer: 1 Part (%d commitment points, %d rows) + %d Acks of %d values"
+        "config": {"workload": name + ": SyncKeyGen N=%d producer: 1 Part (%d commitment points, %d rows) + %d Acks of %d values"
                    % (n, (t + 1) * (t + 2) // 2, n, n_parts, n), "N": n, "t": t, "parts": n_parts,
                    "encryptions": n_enc},
         "part_ms": round(t_part[0] / steps * 1e3, 3), "acks_ms": round(t_acks[0] / steps * 1e3, 3),
@@ -1494,7 +1503,7 @@ def main():
     try:
         for c in args.configs.split(","):
             steps = args.steps if args.steps is not None else STEPS_DEFAULT.get(c, 2)
-            warmup = args.warmup if args.warmup is not None else (1 if c in ("c5", "c5p", "kg") else 2)
+            warmup = args.warmup if args.warmup is not None else (1 if c in ("c5", "c5p", "c5p1", "kg") else 2)
             if c == "c1":
                 out = bench_c1(ctx, steps, warmup, cpu_budget=0.0 if args.no_cpu else 10.0)
             elif c == "c2":
@@ -1516,8 +1525,9 @@ def main():
                 out = bench_coin_round(ctx, steps, warmup)
             elif c == "kg":
                 out = bench_keygen(ctx, args.nodes, steps, warmup, parent=args.kg_parent)
-            elif c == "c5p":
-                out = bench_skg_producer(ctx, args.nodes, min(args.parts, args.nodes), steps, warmup)
+            elif c in ("c5p", "c5p1"):
+                out = bench_skg_producer(ctx, args.nodes, min(args.parts, args.nodes), steps, warmup,
+                                         one_call=c == "c5p1")
             elif c == "c5":
                 out = bench_skg(ctx, 1000, args.parts, args.distinct, steps, warmup,
                                 cpu_budget=0.0 if args.no_cpu else 10.0)

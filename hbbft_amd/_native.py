@@ -124,6 +124,8 @@ SIGNATURES = {
     "hbtc_verify_signed_msgs": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P]),
     "hbtc_fr_poly_eval": (_I32, [_P, _U32, _U32, _P, _U32, _P, _P]),
     "hbtc_skg_generate": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    "hbtc_skg_part": (_I32, [_P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hbtc_skg_acks": (_I32, [_P, _U32, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "hbtc_unframe_points_dev": (_I32, [_P, _U32, _U32, _P, _P]),
     "hbtc_stream_wait_ctx": (_I32, [_P, _P]),
     "hbtc_ctx_wait_stream": (_I32, [_P, _P]),
@@ -156,6 +158,10 @@ SIGNATURES = {
     "hbtc_node_combine_dec_verified_dev": (_I32, [_P, _P, _U32]),
     "hbtc_node_sync": (_I32, [_P]),
 }
+
+
+# items of one hbtc_skg_acks call (hbtc.h); Context.skg_acks splits a larger batch by whole rows
+SKG_ACKS_MAX_ITEMS = 1 << 20
 
 
 class NodePart(ctypes.Structure):
@@ -937,6 +943,67 @@ class Context:
         self._check(self.lib.hbtc_fr_poly_eval(self.h, n_poly, n_coeff, _ptr(cb), n_x, _ptr(xb),
                                                _ptr(out)), "hbtc_fr_poly_eval")
         return out.reshape(n_poly, n_x, 32)
+
+    # ---- SyncKeyGen::new's Part and the Acks, one call each
+    def skg_part(self, keyset_id, n_nodes, t, bcoef, rs):
+        """hbtc_skg_part: our Part for the n_nodes recipients of the loaded key set keyset_id.
+        bcoef: the (t + 1)(t + 2) / 2 packed coefficients (ints below 2^256); rs: n_nodes encryption
+        scalars.  Returns (commit [48 B each], [(u, v, w)] per node, status); the entries of a key
+        that did not load are zero-filled (status DECODE_ERR)."""
+        t, n = int(t), int(n_nodes)
+        m, ln = (t + 1) * (t + 2) // 2, 8 + 40 * (t + 1)
+        b, sc = self._fr_bytes(bcoef), self._fr_bytes(rs)
+        if b is bcoef or b.base is not None:
+            b = b.copy()  # a packed copy of our own: it is cleared below, the caller's array is not
+        commit = np.zeros(48 * m, np.uint8)
+        u, v, w = np.zeros(48 * n, np.uint8), np.zeros(ln * n, np.uint8), np.zeros(96 * n, np.uint8)
+        st = np.zeros(n, np.int32)
+        try:
+            if b.size != 32 * m or sc.size != 32 * n:
+                raise ValueError("(t + 1)(t + 2) / 2 coefficients and one scalar per node")
+            self._check(self.lib.hbtc_skg_part(self.h, keyset_id, t, _ptr(b), _ptr(sc), _ptr(commit), _ptr(u),
+                                               _ptr(v), _ptr(w), _ptr(st)), "hbtc_skg_part")
+        finally:
+            b[:] = 0
+        cb, ub, vb, wb = commit.tobytes(), u.tobytes(), v.tobytes(), w.tobytes()
+        return ([cb[48 * k:48 * k + 48] for k in range(m)],
+                [(ub[48 * i:48 * i + 48], vb[ln * i:ln * i + ln], wb[96 * i:96 * i + 96]) for i in range(n)], st)
+
+    def skg_acks(self, keyset_id, n_nodes, rows, rs):
+        """hbtc_skg_acks: for every verified row (equally long lists of ints below 2^256) its value
+        at 1 .. n_nodes encrypted to the nodes of the loaded key set; rs: len(rows) * n_nodes
+        encryption scalars.  Returns ([(u, v, w)], status), item a * n_nodes + i = row a to node i.
+        A batch of more than SKG_ACKS_MAX_ITEMS items goes as several calls of whole rows."""
+        n_rows, n = len(rows), int(n_nodes)
+        n_coeff = len(rows[0]) if n_rows else 0
+        if any(len(r) != n_coeff for r in rows):
+            raise ValueError("rows of equal length")
+        sc = self._fr_bytes(rs)
+        if sc.size != 32 * n_rows * n:
+            raise ValueError("one scalar per row and node")
+        if n_rows * n == 0:
+            return [], np.zeros(0, np.int32)
+        if n > SKG_ACKS_MAX_ITEMS:
+            raise ValueError("more nodes than the items of one hbtc_skg_acks call")
+        per = max(1, SKG_ACKS_MAX_ITEMS // n)
+        cts, sts = [], []
+        for a0 in range(0, n_rows, per):
+            a1 = min(n_rows, a0 + per)
+            k = (a1 - a0) * n
+            rb = self._fr_bytes([c for r in rows[a0:a1] for c in r]) if n_coeff else None
+            u, v, w = np.zeros(48 * k, np.uint8), np.zeros(40 * k, np.uint8), np.zeros(96 * k, np.uint8)
+            st = np.zeros(k, np.int32)
+            try:
+                self._check(self.lib.hbtc_skg_acks(self.h, keyset_id, a1 - a0, n_coeff, _ptr(rb),
+                                                   _ptr(sc[32 * a0 * n:32 * a1 * n]), _ptr(u), _ptr(v), _ptr(w),
+                                                   _ptr(st)), "hbtc_skg_acks")
+            finally:
+                if rb is not None:
+                    rb[:] = 0
+            ub, vb, wb = u.tobytes(), v.tobytes(), w.tobytes()
+            cts += [(ub[48 * i:48 * i + 48], vb[40 * i:40 * i + 40], wb[96 * i:96 * i + 96]) for i in range(k)]
+            sts.append(st)
+        return cts, np.concatenate(sts)
 
     # ---- SyncKeyGen::generate + NetworkInfo::new
     def skg_generate(self, t, row0, values, n_nodes, load_keyset=False, want_shares=True):

@@ -14,6 +14,7 @@
 
 #include "hbtc_kernels.h"
 #include "own_host.h"
+#include "skgp.h"
 
 using namespace hbtc;
 
@@ -4146,6 +4147,21 @@ int hbtc_verify_signed_msgs(hbtc_ctx* c, uint32_t keyset_id, uint32_t n, const u
   return HBTC_OK;
 }
 
+// The window table of the G1 generator (enc.h), built at the first call that needs it.
+static int enc_table_ready(hbtc_ctx* c) {
+  if (c->enc_tab) return HBTC_OK;
+  EncPt* tab = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&tab), ENC_TAB_BYTES) != hipSuccess)
+    return fail(c, HBTC_ERR_OOM, "hipMalloc enc.tab");
+  const hipError_t e = launch_enc_table(c->stream, tab);
+  if (e != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(tab);
+    return fail(c, HBTC_ERR_DEVICE, std::string("enc table: ") + hipGetErrorString(e));
+  }
+  c->enc_tab = tab;  // every lane's stream may read it from here on
+  return HBTC_OK;
+}
+
 int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_stride,
                  const uint8_t* r_le32, const uint8_t* msgs, const uint32_t* offsets,
                  uint8_t* out_u_c48, uint8_t* out_v, uint8_t* out_w_c96, int32_t* status) {
@@ -4159,17 +4175,7 @@ int hbtc_encrypt(hbtc_ctx* c, uint32_t n, const uint8_t* pk_c48, uint32_t pk_str
   HB_TRY(pad_block_table(c, n, offsets, blk));
   const uint32_t nb = blk[n];
   const size_t total = offsets[n];
-  if (!c->enc_tab) {  // the generator's window table, once per context
-    EncPt* tab = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&tab), ENC_TAB_BYTES) != hipSuccess)
-      return fail(c, HBTC_ERR_OOM, "hipMalloc enc.tab");
-    const hipError_t e = launch_enc_table(c->stream, tab);
-    if (e != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-      (void)hipFree(tab);
-      return fail(c, HBTC_ERR_DEVICE, std::string("enc table: ") + hipGetErrorString(e));
-    }
-    c->enc_tab = tab;  // every lane's stream may read it from here on
-  }
+  HB_TRY(enc_table_ready(c));
   const uint32_t n_pk = pk_stride ? n : 1;
   void *d_pk, *d_r, *d_msgs, *d_off, *d_blk;
   HB_TRY(upload(c, "enc.pk", pk_c48, (size_t)48 * n_pk, &d_pk));
@@ -4402,6 +4408,174 @@ int hbtc_skg_generate(hbtc_ctx* c, uint32_t n_parts, uint32_t t, const uint8_t* 
     *out_keyset_id = keyset_register(c, ks);
   }
   return HBTC_OK;
+}
+
+// hbtc.h hbtc_skg_part / hbtc_skg_acks: one packed upload, the stages of hbtc_skgp.hip and of the
+// encryption back to back on the stream, one packed download, one wait.  The n items all have
+// `len` plaintext bytes (a Part: the N rows' Poly frames and the commitment of the n_sec = (t + 1)
+// (t + 2) / 2 coefficients; Acks: n_rows * N FieldWraps of n_rows rows of n_coeff coefficients), so
+// the offset and pad block tables are written here without a look at the data.  Every copy of the
+// secret scalars, of what the kernels derive from them and of the plaintext frames is cleared
+// before the call returns, whether it succeeds or not.
+static int skgp_call(hbtc_ctx* c, const Keyset& ks, bool part, uint32_t n_rows, uint32_t n_coeff,
+                     const uint8_t* sec_le32, uint32_t n_sec, const uint8_t* r_le32,
+                     uint8_t* out_commit_c48, uint8_t* out_u_c48, uint8_t* out_v, uint8_t* out_w_c96,
+                     int32_t* status) {
+  const uint32_t N = ks.n, n = part ? N : n_rows * N;  // the callers bound n_rows * N
+  const uint32_t len = part ? (uint32_t)skgp_row_bytes(n_coeff) : SKGP_FR_FRAME, bpi = (len + 15) / 16;
+  const uint32_t n_commit = part ? n_sec : 0;
+  const size_t total = (size_t)n * len;  // < 2^32: checked by the callers
+  if ((uint64_t)n * bpi > 0xffffff00ull) return fail(c, HBTC_ERR_ARG, "too many pad blocks in one call");
+  auto pad16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  // the packed input: secret scalars | r | offsets | first pad blocks
+  const size_t in_r = pad16((size_t)32 * n_sec), in_off = in_r + (size_t)32 * n,
+               in_blk = in_off + pad16((size_t)4 * (n + 1)), in_bytes = in_blk + (size_t)4 * (n + 1);
+  // the packed output: commitment | u | v | w | status | redraw flags
+  const size_t o_u = pad16((size_t)48 * n_commit), o_v = o_u + (size_t)48 * n, o_w = o_v + pad16(total),
+               o_st = o_w + (size_t)96 * n, o_flag = o_st + pad16((size_t)4 * n),
+               out_bytes = o_flag + (size_t)4 * n;
+  std::vector<uint8_t> h_in(in_bytes, 0), h_out(out_bytes);
+  if (n_sec) memcpy(h_in.data(), sec_le32, (size_t)32 * n_sec);
+  if (n) memcpy(h_in.data() + in_r, r_le32, (size_t)32 * n);
+  {
+    uint32_t* off = reinterpret_cast<uint32_t*>(h_in.data() + in_off);
+    uint32_t* blk = reinterpret_cast<uint32_t*>(h_in.data() + in_blk);
+    for (uint32_t i = 0; i <= n; ++i) {
+      off[i] = (uint32_t)((size_t)i * len);
+      blk[i] = i * bpi;
+    }
+  }
+  uint8_t *d_in = nullptr, *d_msgs = nullptr;
+  Fr* d_secm = nullptr;
+  uint32_t* d_seed = nullptr;
+  SpanGuard whole;
+  int rc = [&]() -> int {
+    HB_TRY(enc_table_ready(c));
+    HB_TRY(sync(c));
+    uint8_t* d_out;
+    G2A* d_cand;
+    void* p;
+    HB_TRY(wst(c, "skgp.out", out_bytes, &d_out));
+    HB_TRY(wst(c, "skgp.secm", (size_t)n_sec, &d_secm));
+    HB_TRY(wst(c, "skgp.msgs", total, &d_msgs));
+    HB_TRY(wst(c, "enc.seed", (size_t)8 * n, &d_seed));
+    HB_TRY(wst(c, "enc.cand", n, &d_cand));
+    HB_TRY(upload(c, "skgp.in", h_in.data(), in_bytes, &p));
+    d_in = static_cast<uint8_t*>(p);
+    const uint8_t* d_r = d_in + in_r;
+    const uint32_t* d_off = reinterpret_cast<const uint32_t*>(d_in + in_off);
+    const uint32_t* d_blk = reinterpret_cast<const uint32_t*>(d_in + in_blk);
+    uint8_t *d_u = d_out + o_u, *d_v = d_out + o_v, *d_w = d_out + o_w;
+    int32_t* d_st = reinterpret_cast<int32_t*>(d_out + o_st);
+    uint32_t* d_flag = reinterpret_cast<uint32_t*>(d_out + o_flag);
+    HB_TRY(span_begin(c, whole.sp));
+    if (n_commit)
+      HB_TRY(timed(c, "skgp_commit", [&] { return launch_skgp_commit(c->stream, n_commit, d_in, c->enc_tab, d_out); }));
+    if (n)
+      HB_TRY(timed(c, "skgp_frame", [&] {
+        const hipError_t e = launch_fr_to_mont(c->stream, n_sec, d_in, d_secm);
+        if (e != hipSuccess) return e;
+        if (part) return launch_skgp_rows(c->stream, N, n_coeff, d_secm, d_msgs);
+        return launch_skgp_vals(c->stream, n_rows, N, n_coeff, d_secm, d_msgs);
+      }));
+    HB_TRY(timed(c, "enc_g1", [&] {
+      return launch_enc_g1_rcpt(c->stream, n, ks.pk, ks.st, N, d_r, c->enc_tab, d_u, d_seed, d_st);
+    }));
+    HB_TRY(timed(c, "enc_pad", [&] {
+      return launch_enc_pad(c->stream, n, n * bpi, d_blk, d_off, d_seed, d_st, d_msgs, d_v);
+    }));
+    HB_TRY(timed(c, "hash", [&] { return launch_hash_cand(c->stream, n, d_u, d_v, d_off, d_cand); }));
+    HB_TRY(timed(c, "enc_w", [&] { return launch_enc_w(c->stream, n, d_cand, d_r, d_st, d_w, d_flag); }));
+    HB_TRY(span_end(c, whole.sp, part ? "skg_part" : "skg_acks"));
+    whole.handed = c->timing;
+    return download(c, h_out.data(), d_out, out_bytes);
+  }();
+  // nothing of the polynomial, the rows, the frames or the pads stays on the device or in h_in
+  hipError_t ez = hipSuccess;
+  auto zero = [&](void* p, size_t words) {
+    if (!p || !words) return;
+    const hipError_t e = launch_zero_u32(c->stream, static_cast<uint32_t*>(p), words);
+    if (ez == hipSuccess) ez = e;
+  };
+  zero(d_in, (size_t)8 * n_sec);
+  zero(d_secm, (size_t)8 * n_sec);
+  zero(d_msgs, total / 4);
+  zero(d_seed, (size_t)8 * n);
+  const int rs = sync(c);
+  {
+    volatile uint8_t* p = h_in.data();
+    for (size_t i = 0; i < (size_t)32 * n_sec; ++i) p[i] = 0;
+  }
+  HB_TRY(rc);
+  HB_TRY(rs);
+  if (ez != hipSuccess) return fail(c, HBTC_ERR_DEVICE, "skg producer: the secret staging copies were not cleared");
+  if (n_commit) memcpy(out_commit_c48, h_out.data(), (size_t)48 * n_commit);
+  if (n == 0) return HBTC_OK;
+  memcpy(out_u_c48, h_out.data() + o_u, (size_t)48 * n);
+  memcpy(out_v, h_out.data() + o_v, total);
+  memcpy(out_w_c96, h_out.data() + o_w, (size_t)96 * n);
+  memcpy(status, h_out.data() + o_st, (size_t)4 * n);
+  // [h2] cand = O (probability ~2^-250, never observed): redone as hbtc_encrypt redoes it
+  const uint32_t* flag = reinterpret_cast<const uint32_t*>(h_out.data() + o_flag);
+  std::vector<uint32_t> redo;
+  for (uint32_t i = 0; i < n; ++i)
+    if (status[i] == HBTC_ACCEPT && flag[i]) redo.push_back(i);
+  if (!redo.empty()) {
+    const uint32_t m = (uint32_t)redo.size();
+    std::vector<uint8_t> H((size_t)96 * m), k((size_t)32 * m), w((size_t)96 * m);
+    std::vector<int32_t> st(m);
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t i = redo[j];
+      hash_g1_g2_c96(out_u_c48 + 48 * (size_t)i, out_v + (size_t)i * len, len, H.data() + 96 * (size_t)j);
+      memcpy(k.data() + 32 * (size_t)j, r_le32 + 32 * (size_t)i, 32);
+    }
+    HB_TRY(point_mul_host(c, 2, m, H.data(), 1, k.data(), w.data(), st.data()));
+    for (uint32_t j = 0; j < m; ++j) {
+      if (st[j] != HBTC_ACCEPT) return fail(c, HBTC_ERR_DEVICE, "skg producer: the hash point failed to decode");
+      memcpy(out_w_c96 + 96 * (size_t)redo[j], w.data() + 96 * (size_t)j, 96);
+    }
+  }
+  return HBTC_OK;
+}
+
+static int skgp_keyset(hbtc_ctx* c, uint32_t id, Keyset** ks) {
+  auto it = c->keysets.find(id);
+  if (it == c->keysets.end()) return fail(c, HBTC_ERR_ARG, "unknown keyset id");
+  *ks = &it->second;
+  return HBTC_OK;
+}
+
+int hbtc_skg_part(hbtc_ctx* c, uint32_t keyset_id, uint32_t t, const uint8_t* bcoef_le32,
+                  const uint8_t* r_le32, uint8_t* out_commit_c48, uint8_t* out_u_c48, uint8_t* out_v,
+                  uint8_t* out_w_c96, int32_t* status) {
+  if (!c || !bcoef_le32 || !out_commit_c48) return HBTC_ERR_ARG;
+  Guard g(c);
+  const uint64_t t1 = (uint64_t)t + 1, n_commit = t1 * (t1 + 1) / 2;
+  if (n_commit > (1ull << 26)) return fail(c, HBTC_ERR_ARG, "skg_part: more than 2^26 coefficients");
+  Keyset* ks;
+  HB_TRY(skgp_keyset(c, keyset_id, &ks));
+  if (ks->n && (!r_le32 || !out_u_c48 || !out_v || !out_w_c96 || !status))
+    return fail(c, HBTC_ERR_ARG, "skg_part: NULL buffer");
+  if ((uint64_t)ks->n * skgp_row_bytes((uint32_t)t1) >= (1ull << 32))
+    return fail(c, HBTC_ERR_ARG, "skg_part: 2^32 or more bytes of rows in one call");
+  return skgp_call(c, *ks, true, ks->n, (uint32_t)t1, bcoef_le32, (uint32_t)n_commit, r_le32, out_commit_c48,
+                   out_u_c48, out_v, out_w_c96, status);
+}
+
+int hbtc_skg_acks(hbtc_ctx* c, uint32_t keyset_id, uint32_t n_rows, uint32_t n_coeff,
+                  const uint8_t* rows_le32, const uint8_t* r_le32, uint8_t* out_u_c48, uint8_t* out_v,
+                  uint8_t* out_w_c96, int32_t* status) {
+  if (!c || !r_le32 || !out_u_c48 || !out_v || !out_w_c96 || !status) return HBTC_ERR_ARG;
+  Guard g(c);
+  Keyset* ks;
+  HB_TRY(skgp_keyset(c, keyset_id, &ks));
+  const uint64_t n = (uint64_t)n_rows * ks->n, n_sec = (uint64_t)n_rows * n_coeff;
+  if (n == 0) return fail(c, HBTC_ERR_ARG, "skg_acks: no items");
+  if (n > (1ull << 20)) return fail(c, HBTC_ERR_ARG, "skg_acks: more than 2^20 items in one call");
+  if (n_sec > (1ull << 26)) return fail(c, HBTC_ERR_ARG, "skg_acks: more than 2^26 coefficients");
+  if (n_sec && !rows_le32) return fail(c, HBTC_ERR_ARG, "skg_acks: NULL rows");
+  return skgp_call(c, *ks, false, n_rows, n_coeff, rows_le32, (uint32_t)n_sec, r_le32, nullptr, out_u_c48,
+                   out_v, out_w_c96, status);
 }
 
 }  // extern "C"

@@ -49,16 +49,12 @@ __global__ void __launch_bounds__(64) k_enc_table(EncPt* __restrict__ tab) {
 
 // One lane per item: u = r G1 from the table, g = r pk by the GLV split, both made affine with
 // one shared inversion; u is stored compressed, g only as the ChaCha seed of its pad.
-__global__ void __launch_bounds__(64) k_enc_g1(uint32_t n, const G1A* __restrict__ pk,
-                                               const int32_t* __restrict__ pk_st, uint32_t pk_stride,
-                                               const uint8_t* __restrict__ r_le32,
-                                               const EncPt* __restrict__ tab,
-                                               uint32_t* __restrict__ out_u,
-                                               uint32_t* __restrict__ seeds,
-                                               int32_t* __restrict__ status) {
-  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  const size_t pi = (size_t)i * pk_stride;
+// (item i with the key at index pi: the body of k_enc_g1 and k_enc_g1_rcpt)
+__device__ __forceinline__ void enc_g1_item(uint32_t i, size_t pi, const G1A* __restrict__ pk,
+                                            const int32_t* __restrict__ pk_st,
+                                            const uint8_t* __restrict__ r_le32,
+                                            const EncPt* __restrict__ tab, uint32_t* __restrict__ out_u,
+                                            uint32_t* __restrict__ seeds, int32_t* __restrict__ status) {
   uint32_t w[12], seed[8];
   if (pk_st[pi] != HBTC_ACCEPT) {
     for (int j = 0; j < 12; ++j) w[j] = 0;
@@ -88,6 +84,32 @@ __global__ void __launch_bounds__(64) k_enc_g1(uint32_t n, const G1A* __restrict
   enc_pad_seed(seed, w);
   enc_store_words(seeds, i, seed, 8);
   status[i] = HBTC_ACCEPT;
+}
+
+__global__ void __launch_bounds__(64) k_enc_g1(uint32_t n, const G1A* __restrict__ pk,
+                                               const int32_t* __restrict__ pk_st, uint32_t pk_stride,
+                                               const uint8_t* __restrict__ r_le32,
+                                               const EncPt* __restrict__ tab,
+                                               uint32_t* __restrict__ out_u,
+                                               uint32_t* __restrict__ seeds,
+                                               int32_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  enc_g1_item(i, (size_t)i * pk_stride, pk, pk_st, r_le32, tab, out_u, seeds, status);
+}
+
+// The recipient-indexed form (hbtc_skg_part / hbtc_skg_acks): item i goes to key i % n_keys of a
+// loaded key set, whose decoded points and statuses are read in place.
+__global__ void __launch_bounds__(64) k_enc_g1_rcpt(uint32_t n, const G1A* __restrict__ pk,
+                                                    const int32_t* __restrict__ pk_st, uint32_t n_keys,
+                                                    const uint8_t* __restrict__ r_le32,
+                                                    const EncPt* __restrict__ tab,
+                                                    uint32_t* __restrict__ out_u,
+                                                    uint32_t* __restrict__ seeds,
+                                                    int32_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  enc_g1_item(i, i % n_keys, pk, pk_st, r_le32, tab, out_u, seeds, status);
 }
 
 // v = msg XOR hash_bytes(g, |msg|): one lane per 16-byte block of the pad, so a long message (a
@@ -243,6 +265,15 @@ hipError_t launch_enc_g1(hipStream_t s, uint32_t n, const G1A* pk, const int32_t
                          uint32_t* seeds, int32_t* status) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_enc_g1, dim3(enc_blocks(n, 64)), dim3(64), 0, s, n, pk, pk_st, pk_stride, r_le32,
+                     tab, reinterpret_cast<uint32_t*>(out_u), seeds, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_enc_g1_rcpt(hipStream_t s, uint32_t n, const G1A* pk, const int32_t* pk_st,
+                              uint32_t n_keys, const uint8_t* r_le32, const EncPt* tab, uint8_t* out_u,
+                              uint32_t* seeds, int32_t* status) {
+  if (n == 0 || n_keys == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_enc_g1_rcpt, dim3(enc_blocks(n, 64)), dim3(64), 0, s, n, pk, pk_st, n_keys, r_le32,
                      tab, reinterpret_cast<uint32_t*>(out_u), seeds, status);
   return hipGetLastError();
 }

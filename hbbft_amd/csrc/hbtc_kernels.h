@@ -422,6 +422,10 @@ hipError_t launch_enc_table(hipStream_t s, EncPt* tab);
 hipError_t launch_enc_g1(hipStream_t s, uint32_t n, const G1A* pk, const int32_t* pk_st,
                          uint32_t pk_stride, const uint8_t* r_le32, const EncPt* tab, uint8_t* out_u,
                          uint32_t* seeds, int32_t* status);
+// the same with item i encrypted to key i % n_keys of a loaded key set's decoded points / statuses
+hipError_t launch_enc_g1_rcpt(hipStream_t s, uint32_t n, const G1A* pk, const int32_t* pk_st,
+                              uint32_t n_keys, const uint8_t* r_le32, const EncPt* tab, uint8_t* out_u,
+                              uint32_t* seeds, int32_t* status);
 // v = msg XOR pad, one lane per 16-byte pad block; blk_off: n + 1 first-block indices
 hipError_t launch_enc_pad(hipStream_t s, uint32_t n, uint32_t n_blocks, const uint32_t* blk_off,
                           const uint32_t* offsets, const uint32_t* seeds, const int32_t* status,
@@ -446,6 +450,17 @@ hipError_t launch_fr_to_mont(hipStream_t s, uint64_t n, const uint8_t* in_le32, 
 // out[p * n_x + j] = poly_p(x_j), canonical; coeffs / xs in Montgomery form
 hipError_t launch_fr_poly_eval(hipStream_t s, uint32_t n_poly, uint32_t n_coeff, const Fr* coeffs,
                                uint32_t n_x, const Fr* xs, uint8_t* out_le32);
+
+// ---- SyncKeyGen::new's Part and the Acks (hbtc_skgp.hip, arithmetic in skgp.h)
+// out[k] = bcoef[k] G1 (compressed; any 256-bit bcoef), two coefficients per lane
+hipError_t launch_skgp_commit(hipStream_t s, uint32_t n, const uint8_t* bcoef_le32, const EncPt* tab,
+                              uint8_t* out_c48);
+// msgs = the Poly frames (8 + 40 t1 bytes each) of rows 1 .. n_rows of the packed triangle bm
+// (Montgomery form)
+hipError_t launch_skgp_rows(hipStream_t s, uint32_t n_rows, uint32_t t1, const Fr* bm, uint8_t* msgs);
+// msgs[(a * n_nodes + i) * 40 ..] = the FieldWrap of row_a(i + 1); rows_m in Montgomery form
+hipError_t launch_skgp_vals(hipStream_t s, uint32_t n_rows, uint32_t n_nodes, uint32_t n_coeff,
+                            const Fr* rows_m, uint8_t* msgs);
 
 // ---- SyncKeyGen::generate + NetworkInfo::new (hbtc_keygen.hip, arithmetic in keygen.h)
 // flags: two words, [0] raised by a row0 point that does not decode, [1] by an x repeated inside

@@ -26,6 +26,9 @@ secret share on the device (hbtc_skg_generate); ``generate_keys`` also evaluates
 public key share and leaves them loaded as the new era's key set (NetworkInfo::new,
 src/messaging.rs:253-256) in the same call; ``public_key_shares`` is Commitment::evaluate(i + 1)
 for every node of a given commitment (hbtc_commitment_evaluate).
+Producing: ``SyncKeyGen.new`` and ``_emit_acks`` compose g1_mul, hbtc_fr_poly_eval, the numpy
+framing and hbtc_encrypt; with ``one_call=True`` they are one hbtc_skg_part / hbtc_skg_acks call
+each, the recipients a key set loaded once per instance (same bytes for the same scalars).
 Values on the wire use hbbft_amd/wire.py's bincode framing (parity-unpinned Fr layout).
 """
 import secrets
@@ -113,7 +116,7 @@ class _Proposal:
 class SyncKeyGen:
     """One node's SyncKeyGen instance with batched message handling (see module docstring)."""
 
-    def __init__(self, ctx, our_id, sec_key, pub_keys, threshold):
+    def __init__(self, ctx, our_id, sec_key, pub_keys, threshold, one_call=False):
         self.ctx = ctx
         self.our_id = our_id
         self.sec_key = int(sec_key)
@@ -124,15 +127,45 @@ class SyncKeyGen:
         self.t = int(threshold)
         self.parts = {}
         self.queue = []
+        # one_call: our Part and our Acks through hbtc_skg_part / hbtc_skg_acks, the recipients a key
+        # set loaded once here (an observer produces nothing and loads nothing)
+        self.one_call = bool(one_call) and self.our_idx is not None
+        self.rcpt_keyset = None
+        if self.one_call:
+            self.rcpt_keyset, bad = ctx.keyset_load([self.pub_keys[n] for n in self.ids])
+            if bad:
+                self.close()
+                raise N.HbtcError("encrypt: a public key failed to decode")
+
+    def close(self):
+        """Free the recipients' key set of a one_call instance."""
+        kid, self.rcpt_keyset = self.rcpt_keyset, None
+        if kid is not None and getattr(self.ctx, "h", None):
+            self.ctx.keyset_free(kid)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     @classmethod
-    def new(cls, ctx, our_id, sec_key, pub_keys, threshold):
-        """SyncKeyGen::new (:293-330): the instance and our Part (None for an observer)."""
-        kg = cls(ctx, our_id, sec_key, pub_keys, threshold)
+    def new(cls, ctx, our_id, sec_key, pub_keys, threshold, one_call=False):
+        """SyncKeyGen::new (:293-330): the instance and our Part (None for an observer).  one_call:
+        the Part and the instance's Acks are made by one device call each (hbtc_skg_part,
+        hbtc_skg_acks) instead of the composed g1_mul / fr_poly_eval / encrypt calls; same bytes."""
+        kg = cls(ctx, our_id, sec_key, pub_keys, threshold, one_call)
         if kg.our_idx is None:
             return kg, None
         t = kg.t
         b = [secrets.randbelow(R) for _ in range((t + 1) * (t + 2) // 2)]  # BivarPoly::random
+        if kg.one_call:
+            n = len(kg.ids)
+            rs = [secrets.randbelow(R - 1) + 1 for _ in range(n)]
+            commit, cts, st = ctx.skg_part(kg.rcpt_keyset, n, t, b, rs)
+            if st.any():
+                raise N.HbtcError("encrypt: a public key failed to decode")
+            return kg, Part(commit, [Ciphertext(u, v, w) for u, v, w in cts])
         cm, st = ctx.g1_mul(G1_GEN, _fr_le(b))
         if st.any():
             raise N.HbtcError("commitment failed")
@@ -285,6 +318,15 @@ class SyncKeyGen:
         if not new_acks:
             return
         n = len(self.ids)
+        if self.one_call:
+            rs = [secrets.randbelow(R - 1) + 1 for _ in range(n * len(new_acks))]
+            raw, st = self.ctx.skg_acks(self.rcpt_keyset, n, [list(row) for _, _, row in new_acks], rs)
+            if st.any():
+                raise N.HbtcError("encrypt: a public key failed to decode")
+            cts = [Ciphertext(u, v, w) for u, v, w in raw]
+            for a, (m, s_idx, _) in enumerate(new_acks):
+                out[m] = ("valid", Ack(s_idx, cts[a * n:(a + 1) * n]))
+            return
         msgs = [m for vals in ack_values(self.ctx, [row for _, _, row in new_acks], n) for m in vals]
         pks = [self.pub_keys[self.ids[i]] for i in range(n)] * len(new_acks)
         cts = encrypt_batch(self.ctx, pks, msgs)

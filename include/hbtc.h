@@ -30,6 +30,8 @@
  *   hbtc_skg_generate        SyncKeyGen::generate + NetworkInfo::new: the era's PublicKeySet, our secret key
  *                            share and every public key share, loaded as a key set
  *                                                                             src/sync_key_gen.rs:428-447, src/messaging.rs:253-256
+ *   hbtc_skg_part            SyncKeyGen::new's Part: the commitment and the N encrypted rows     src/sync_key_gen.rs:293-330
+ *   hbtc_skg_acks            the Acks of verified Parts: row(i + 1) encrypted to every node      src/sync_key_gen.rs:371-380
  *   hbtc_decrypt_shares      SecretKeyShare::decrypt_share (hash_g1_g2, Ciphertext::verify, sk u) for every
  *                            accepted proposer's ciphertext   src/threshold_decryption.rs:94-113
  *   hbtc_sign_shares         SecretKeyShare::sign (hash_g2, sk H): the node's own coin shares
@@ -279,6 +281,44 @@ int hbtc_skg_generate(hbtc_ctx* ctx, uint32_t n_parts, uint32_t t, const uint8_t
                       const uint32_t* val_offsets, const uint32_t* val_x, const uint8_t* vals_le32,
                       uint32_t n_nodes, uint8_t* out_commit_c48, uint8_t* out_pk_shares_c48,
                       uint8_t* out_sk_le32, uint32_t* out_keyset_id, int32_t* status);
+
+/* The producing half of a SyncKeyGen era in one call each (DESIGN.md, section 5 "SyncKeyGen producer
+ * in one call"): one upload, every stage back to back on one stream, one download, one wait.
+ * The recipients are the N keys of a loaded key set (hbtc_keyset_load of the nodes' individual
+ * public keys in node order): item i is encrypted to key i mod N, whose decoded point and status
+ * are read from the key set, so no key is decoded again.  Every scalar is 32 bytes little-endian,
+ * any value below 2^256, taken mod r.
+ *
+ * hbtc_skg_part, SyncKeyGen::new's Part (src/sync_key_gen.rs:293-330):
+ *   bcoef_le32      the (t + 1)(t + 2) / 2 coefficients of the symmetric bivariate polynomial,
+ *                   packed upper triangle in BivarPoly::coeff_pos order
+ *   r_le32          the N encryption scalars
+ *   out_commit_c48[k] = bcoef[k] G1, byte-equal to hbtc_g1_mul on the generator (a coefficient = 0
+ *                   mod r gives the infinity encoding)
+ *   ciphertext x - 1 (x = 1 .. N) encrypts the bincode Poly of row x, whose coefficient k is
+ *                   sum_j bcoef[coeff_pos(k, j)] x^j: the count t + 1 as a u64 little-endian, then per
+ *                   coefficient a u64 little-endian 32 and the 32 bytes big-endian; v_i is
+ *                   8 + 40 (t + 1) bytes, out_v holds them back to back
+ * hbtc_skg_acks, the Acks of n_rows verified Parts (src/sync_key_gen.rs:371-380):
+ *   rows_le32       n_rows rows of n_coeff coefficients, constant term first (may be NULL when
+ *                   n_coeff == 0: every value is 0 then)
+ *   r_le32          n_rows * N encryption scalars
+ *   item a * N + i encrypts the 40-byte bincode FieldWrap of row_a(i + 1) to key i
+ * (u, v, w) and status of every item are byte-equal to hbtc_encrypt on the same key bytes, scalar
+ * and plaintext: a key that did not load gives HBTC_DECODE_ERR and zero-filled outputs, the
+ * infinity key is accepted, r = 0 mod r gives u = w = infinity.
+ * HBTC_ERR_ARG: a NULL context or a NULL required buffer (every buffer but rows_le32 with
+ * n_coeff == 0), an unknown key set, n_rows * N == 0, 2^32 or more bytes of out_v, more than 2^26
+ * coefficients, more than 2^20 items in one hbtc_skg_acks call (split a larger batch by whole rows).
+ * The polynomial, the rows and the values are the node's secret material: every host and device
+ * staging copy of the scalars, of their Montgomery forms, of the unencrypted frames and of the pad
+ * seeds is overwritten with zeros before the call returns, on every exit path. */
+int hbtc_skg_part(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t t, const uint8_t* bcoef_le32,
+                  const uint8_t* r_le32, uint8_t* out_commit_c48, uint8_t* out_u_c48, uint8_t* out_v,
+                  uint8_t* out_w_c96, int32_t* status);
+int hbtc_skg_acks(hbtc_ctx* ctx, uint32_t keyset_id, uint32_t n_rows, uint32_t n_coeff,
+                  const uint8_t* rows_le32, const uint8_t* r_le32, uint8_t* out_u_c48, uint8_t* out_v,
+                  uint8_t* out_w_c96, int32_t* status);
 
 /* ---- this node's own shares ----------------------------------------------------------------- */
 /* SecretKeyShare::decrypt_share for n ciphertexts (u_i, v_i, w_i) under ONE secret key share
@@ -744,7 +784,10 @@ int hbtc_merkle_validate_dev(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const 
  * stages counting under "hash", the pair check's families ("pb_items", "pb_lines", "pb_ml",
  * "pb_checks" of the pair batch; "pb_decode", "sig_items", "chk_leaves" of the exact checks) and
  * "mul"; "sv_items" (signature decode and the item pass), "sv_sums" (the signers' trees) and
- * "sv_checks" (the signer-level pair checks) of hbtc_verify_signed_msgs.  Reading
+ * "sv_checks" (the signer-level pair checks) of hbtc_verify_signed_msgs; "skg_part" and "skg_acks"
+ * (hbtc_skg_part / hbtc_skg_acks, each the whole call on the device), their stages "skgp_commit"
+ * (k_skgp_commit), "skgp_frame" (the Montgomery conversion and k_skgp_rows / k_skgp_vals) and the
+ * encryption's "enc_g1", "enc_pad", "hash", "enc_w".  Reading
  * synchronises the stream. */
 int hbtc_timing_enable(hbtc_ctx* ctx, int enable);
 int hbtc_timing_read(hbtc_ctx* ctx, const char* family, double* total_ms, uint64_t* launches);

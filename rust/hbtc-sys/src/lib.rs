@@ -14,6 +14,7 @@
 //!   SyncKeyGen::handle_part / handle_ack                  skg_check_parts / skg_check_acks / decrypt
 //!   HoneyBadger::propose, SyncKeyGen::new / Ack values     encrypt / fr_poly_eval (src/sync_key_gen.rs:320-322,372-379)
 //!   SyncKeyGen::generate + NetworkInfo::new               skg_generate        (src/sync_key_gen.rs:428-447)
+//!   SyncKeyGen::new's Part / the Acks, one call each      skg_part / skg_acks (src/sync_key_gen.rs:293-330,371-380)
 #![allow(clippy::too_many_arguments)]
 pub mod ffi;
 #[cfg(feature = "experimental-queues")]
@@ -409,7 +410,60 @@ impl Context {
             status,
         })
     }
+
+    /// SyncKeyGen::new's Part in one call (src/sync_key_gen.rs:293-330; written against the C ABI
+    /// and, like the rest of this crate, not compiled in this repository's checks).  The recipients
+    /// are the `n_nodes` keys of the loaded key set `keyset_id`.  `bcoef_le32`: the
+    /// (t + 1)(t + 2) / 2 packed coefficients; `r_le32`: one encryption scalar per node.  Returns
+    /// (commitment, u, v with 8 + 40 (t + 1) bytes per node, w, status).
+    pub fn skg_part(&self, keyset_id: u32, n_nodes: usize, t: u32, bcoef_le32: &[u8], r_le32: &[u8])
+        -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<i32>)> {
+        let t1 = t as usize + 1;
+        let m = t1 * (t1 + 1) / 2;
+        assert_eq!(bcoef_le32.len(), 32 * m, "(t + 1)(t + 2) / 2 coefficients");
+        assert_eq!(r_le32.len(), 32 * n_nodes, "one 32-byte scalar per node");
+        let mut commit = vec![0u8; 48 * m];
+        let (mut u, mut v, mut w, mut st) =
+            (vec![0u8; 48 * n_nodes], vec![0u8; (8 + 40 * t1) * n_nodes], vec![0u8; 96 * n_nodes], vec![0i32; n_nodes]);
+        self.ok(unsafe {
+            ffi::hbtc_skg_part(self.raw, keyset_id, t, bcoef_le32.as_ptr(), r_le32.as_ptr(), commit.as_mut_ptr(),
+                               u.as_mut_ptr(), v.as_mut_ptr(), w.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        Ok((commit, u, v, w, st))
+    }
+
+    /// The Acks of verified Parts in one call per chunk of whole rows (src/sync_key_gen.rs:371-380;
+    /// not compiled in this repository's checks either).  `rows_le32`: rows of `n_coeff`
+    /// coefficients; `r_le32`: one scalar per (row, node).  Item a * n_nodes + i is row a's value at
+    /// i + 1 encrypted to node i.  Returns (u, v with 40 bytes per item, w, status).
+    pub fn skg_acks(&self, keyset_id: u32, n_nodes: usize, n_coeff: u32, rows_le32: &[u8], r_le32: &[u8])
+        -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<i32>)> {
+        assert!(n_nodes > 0 && n_nodes <= SKG_ACKS_MAX_ITEMS, "between 1 and 2^20 nodes");
+        assert_eq!(r_le32.len() % (32 * n_nodes), 0, "one 32-byte scalar per row and node");
+        let n_rows = r_le32.len() / (32 * n_nodes);
+        let row = 32 * n_coeff as usize;
+        assert_eq!(rows_le32.len(), row * n_rows, "n_coeff coefficients per row");
+        let n = n_rows * n_nodes;
+        let (mut u, mut v, mut w, mut st) = (vec![0u8; 48 * n], vec![0u8; 40 * n], vec![0u8; 96 * n], vec![0i32; n]);
+        let per = SKG_ACKS_MAX_ITEMS / n_nodes;
+        let mut a0 = 0;
+        while a0 < n_rows {
+            let a1 = n_rows.min(a0 + per);
+            let i0 = a0 * n_nodes;
+            self.ok(unsafe {
+                ffi::hbtc_skg_acks(self.raw, keyset_id, (a1 - a0) as u32, n_coeff,
+                                   if row > 0 { rows_le32[row * a0..].as_ptr() } else { ptr::null() },
+                                   r_le32[32 * i0..].as_ptr(), u[48 * i0..].as_mut_ptr(), v[40 * i0..].as_mut_ptr(),
+                                   w[96 * i0..].as_mut_ptr(), st[i0..].as_mut_ptr())
+            })?;
+            a0 = a1;
+        }
+        Ok((u, v, w, st))
+    }
 }
+
+/// Items of one `hbtc_skg_acks` call; `Context::skg_acks` splits a larger batch by whole rows.
+pub const SKG_ACKS_MAX_ITEMS: usize = 1 << 20;
 
 /// What `Context::skg_generate` returns: the PublicKeySet's commitment (t + 1 compressed G1), every
 /// node's public key share, our secret key share (None for an observer), the loaded key set.
