@@ -517,6 +517,23 @@ std::pair<uintptr_t, uintptr_t> rng(const void* p, size_t bytes) {
   return {lo, lo + bytes};
 }
 
+// A device range whose length is known on the device only (the last entry of an offset array in
+// device memory): from p to the end of p's allocation, or open-ended when the runtime does not
+// know the allocation.  Calls on other allocations stay unordered against it.
+std::pair<uintptr_t, uintptr_t> rng_to_end(const void* p) {
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+  if (!p) return {0, 0};
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
+    const uintptr_t hi = reinterpret_cast<uintptr_t>(base) + size;
+    if (hi > lo) return {lo, hi};
+  } else {
+    (void)hipGetLastError();  // not a launch error: keep it out of the launchers' hipGetLastError
+  }
+  return {lo, UINTPTR_MAX};
+}
+
 // `waiter` runs everything enqueued after this behind all work already on `on`.
 int stream_after(hbtc_ctx* c, hipStream_t waiter, hipStream_t on, hipEvent_t ev) {
   HB_CHECK(c, hipEventRecord(ev, on));
@@ -4848,8 +4865,11 @@ int merkle_validate_dev(hbtc_ctx* c, uint32_t n, uint32_t n_nodes, const uint64_
   if (n == 0) return HBTC_OK;
   if ((reinterpret_cast<uintptr_t>(d_dig) & 7u) || (reinterpret_cast<uintptr_t>(d_roots) & 7u))
     return fail(c, HBTC_ERR_ARG, "digests / roots must be 8-byte aligned");
+  // the values and digests end where d_voff[n] and d_doff[n] say, which the host does not see:
+  // each is declared read up to the end of its allocation
   HB_TRY(begin_verify(c, {rng(d_voff, 8 * ((size_t)n + 1)), rng(d_idx, 4 * (size_t)n),
-                          rng(d_doff, 4 * ((size_t)n + 1)), rng(d_roots, 32 * (size_t)n)},
+                          rng(d_doff, 4 * ((size_t)n + 1)), rng(d_roots, 32 * (size_t)n),
+                          rng_to_end(d_values), rng_to_end(d_dig)},
                       {rng(d_status, 4 * (size_t)n)}));
   HB_TRY(timed(c, "merkle_validate", [&] {
     return launch_merkle_validate(c->stream, n, n_nodes, d_voff, d_values, d_idx, d_doff, d_dig, d_roots,

@@ -756,9 +756,23 @@ int hbtc_merkle_trees(hbtc_ctx* ctx, uint32_t n_leaves, uint32_t leaf_len, uint3
 int hbtc_merkle_validate(hbtc_ctx* ctx, uint32_t n, uint32_t n_nodes, const uint64_t* value_off,
                          const uint8_t* values, const uint32_t* index, const uint32_t* digest_off,
                          const uint8_t* digests, const uint8_t* roots, int32_t* status);
-/* Device-pointer forms (ordered on the context's streams like the other *_dev calls; present,
- * status of hbtc_rs_reconstruct_dev and the offsets' last entries stay host-side where noted:
- * present / status are HOST arrays, everything else device memory, digests 8-byte aligned). */
+/* Device-pointer forms: present / status of hbtc_rs_reconstruct_dev are HOST arrays (status is
+ * final when the call returns), everything else is device memory; d_digests and d_roots are
+ * 8-byte aligned, d_shards / d_leaves / d_values may start at any byte.  The calls return once
+ * their work is enqueued.  Consecutive calls rotate over the context's four streams: a call runs
+ * behind the earlier calls of its own stream, and waits for the most recent call of each other
+ * stream only where the device ranges the two touch overlap and one of them writes (a conflict
+ * with a call further back on another stream is not looked for: hbtc_sync between such calls):
+ *   hbtc_rs_encode_dev / hbtc_rs_reconstruct_dev  read and write the n_inst * (k + p) * shard_len
+ *                                                 bytes at d_shards
+ *   hbtc_merkle_trees_dev     reads the n_inst * n_leaves * leaf_len bytes at d_leaves, writes the
+ *                             n_inst * hbtc_merkle_digest_count(n_leaves) * 32 bytes at d_digests
+ *   hbtc_merkle_validate_dev  reads d_value_off, d_index, d_digest_off, d_roots by their lengths,
+ *                             and d_values and d_digests from the pointer given to the END OF ITS
+ *                             ALLOCATION (their lengths are the last offsets, which are in device
+ *                             memory); writes the n statuses at d_status
+ * so a validate may read values or digests an earlier *_dev call produces, and a later call may
+ * overwrite them, without a hbtc_sync between. */
 int hbtc_rs_encode_dev(hbtc_ctx* ctx, uint32_t data_shards, uint32_t parity_shards,
                        uint32_t shard_len, uint32_t n_inst, uint8_t* d_shards);
 int hbtc_rs_reconstruct_dev(hbtc_ctx* ctx, uint32_t data_shards, uint32_t parity_shards,
