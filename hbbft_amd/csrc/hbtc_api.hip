@@ -3480,6 +3480,12 @@ int hbtc_timing_reset(hbtc_ctx* c) {
 }
 
 // ---- hashes with the cofactor clearing on the GPU (the host draws the candidates)
+// the hash batches' message buffer; a batch of empty messages may come without one
+static int upload_msgs(hbtc_ctx* c, const uint8_t* msgs, size_t total, void** out) {
+  if (total == 0) return ws(c, "hash.msgs", 1, out);
+  return upload(c, "hash.msgs", msgs, total, out);
+}
+
 // hash_g2(msg_i) (g1 == null) or hash_g1_g2(g1_i, msg_i) for a batch, entirely on the GPU: the
 // candidate draw (k_hash_cand: sha3, rand 0.4 ChaCha, G2::rand's loop) and [h2] P; a candidate
 // whose [h2] P is O (probability ~2^-250) continues G2::rand's loop on the host (exact).
@@ -3496,7 +3502,7 @@ static int hash_batch_gpu(hbtc_ctx* c, uint32_t n, const uint8_t* g1_c48, const 
   G2A* d_cand;
   uint8_t* d_out;
   int32_t* d_st;
-  HB_TRY(upload(c, "hash.msgs", msgs, offsets[n] ? offsets[n] : 1, &d_msgs));
+  HB_TRY(upload_msgs(c, msgs, offsets[n], &d_msgs));
   HB_TRY(upload(c, "hash.off", offsets, (size_t)4 * (n + 1), &d_off));
   if (g1_c48) HB_TRY(upload(c, "hash.g1", g1_c48, (size_t)48 * n, &d_g1));
   HB_TRY(wst(c, "hash.cand", n, &d_cand));
@@ -3559,12 +3565,6 @@ int hbtc_hash_g1_g2_batch_gpu(hbtc_ctx* c, uint32_t n, const uint8_t* g1_c48, co
     return HBTC_ERR_ARG;
   Guard g(c);
   return hash_batch_gpu(c, n, g1_c48, msgs, offsets, out_c96);
-}
-
-// the hash batches' message buffer; a batch of empty messages may come without one
-static int upload_msgs(hbtc_ctx* c, const uint8_t* msgs, size_t total, void** out) {
-  if (total == 0) return ws(c, "hash.msgs", 1, out);
-  return upload(c, "hash.msgs", msgs, total, out);
 }
 
 // A whole-call timing span whose events are released when the call fails before span_end

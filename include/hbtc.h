@@ -415,7 +415,11 @@ int hbtc_hash_g1_g2_batch(uint32_t n, const uint8_t* g1_c48, const uint8_t* msgs
 /* The same batches with the whole draw on the context's GPU: one lane per message runs the SHA3
  * seed, the ChaCha stream and G2::rand's candidate loop (k_hash_cand), then [h2] P by the psi
  * chain (k_g2_clear_cofactor); the host only redraws in the (never observed) case
- * [h2] P = O. */
+ * [h2] P = O.
+ * n == 0 returns HBTC_OK and leaves out_c96 untouched.  msgs may be NULL when offsets[n] == 0 (a
+ * batch of empty messages: nothing is read through it); a NULL msgs with offsets[n] != 0, a NULL
+ * offsets, out_c96 or (hbtc_hash_g1_g2_batch_gpu) g1_c48, offsets[0] != 0 or decreasing offsets
+ * give HBTC_ERR_ARG. */
 int hbtc_hash_g2_batch_gpu(hbtc_ctx* ctx, uint32_t n, const uint8_t* msgs, const uint32_t* offsets,
                            uint8_t* out_c96);
 int hbtc_hash_g1_g2_batch_gpu(hbtc_ctx* ctx, uint32_t n, const uint8_t* g1_c48,
